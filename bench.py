@@ -10,9 +10,20 @@ frames and state are resident in HBM before the timed region.
     python bench.py [--steps 500] [--warmup 20] [--precision fp64|fp32]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 
+A plain run does what the headline figure needs and no more: set-up, the
+warm-up steps, graph capture, the steps once cold and clock settling (the GPU
+state the timed steps have always started from), the `--steps` timed steps,
+AEPE of their flow, the JSON line (`ms_per_step` = the timed region / steps).
+`--dump-outputs DIR` adds DIR/<name>.npy with what the timed call returned
+(trace, MAP flow, state planes; same seeds, so the same inputs every run).
+`--full` adds every other measurement and check named below: the
+instrumented replay behind `roofline`, the parity gate against
+the CPU paths, the literal-order engine, `strong_scaling` and the strip
+check, C1's host-array call, C3's dominant level, and `cpu_baseline`.
+
 Multi-GPU (default) is frame-parallel (weak scaling): every rank solves its
 own 584x388 pair on its own GPU, no data-path collective; `value` is the
-pixels of all ranks x steps / the slowest rank's time.  The same line carries
+pixels of all ranks x steps / the slowest rank's time.  With --full the line carries
 `strong_scaling`: the RubberWhale pair itself split into one column strip per
 rank (RCCL ghost-column + exact-totals exchange every iteration, lanes per
 node chosen from one strip: gqmap_opticalflow_amd.strip_split), timed the
@@ -467,12 +478,29 @@ def run_engine_config(args, rank, world, local, barrier, engine, names, L, K, ex
     eng.init_state(seed=rank)  # timed steps are iterations 1..steps of the solve
     barrier()
     t0 = time.perf_counter()
-    done, _ = eng.run(args.steps)  # the production path (gqmap_run: graph replay, no instrumentation)
+    done, trace = eng.run(args.steps)  # the production path (gqmap_run: graph replay, no instrumentation)
     barrier()
     elapsed = time.perf_counter() - t0
     if done != args.steps:
         raise RuntimeError(f"rank {rank}: solver stopped after {done}/{args.steps} iterations")
     mp = eng.map()
+    outputs = None
+    if args.dump_outputs:  # what the timed call leaves its caller: the trace, the MAP flow, the state
+        st = eng.get_state()
+        outputs = dict(trace=trace, map=mp, **{k: getattr(st, k) for k in STATE_PLANES})
+    if engine == "super":
+        flow = np.repeat(np.repeat(mp, 4, axis=0), 4, axis=1)
+        a = aepe(flo, flow, unk, 4)
+    else:
+        a = aepe(flo, mp, unk)
+    Mo, No = I1.shape
+    workload = (f"{label}: {name} {No}x{Mo} {engine} L={L} K={K} its={args.steps} "
+                f"(one step = one full-frame iteration)")
+    if not args.full:  # the headline figure alone
+        nodes = eng.M * eng.N
+        eng.close()
+        return dict(elapsed=elapsed, pixels=Mo * No, nodes=nodes, aepe=a, name=name, settle=settle,
+                    outputs=outputs, workload=workload)
     # k_iter durations: the same iterations replayed from the same initial
     # state with a HIP event pair around every launch on the engine's stream
     # (bit-identical work -- checked below; the event markers add a few us
@@ -486,18 +514,15 @@ def run_engine_config(args, rank, world, local, barrier, engine, names, L, K, ex
     mp1 = eng.map()
     # the parity gate compares the GPU flow after gate_its iterations with
     # the CPU paths' (all the timed steps, unless the CPU would take minutes:
-    # the super engine's CPU model runs ~1 s per C4 iteration)
-    gate_its = min(args.steps, args.parity_steps or (args.steps if engine != "super" else 20))
+    # the super engine's CPU model runs ~1 s per C4 iteration, and the C2
+    # gate's five CPU solves take ~0.26 s per iteration together, so past the
+    # config's default 500 steps the gate stays at 500)
+    gate_its = min(args.steps, args.parity_steps or (DEFAULT_STEPS["c2"] if engine != "super" else 20))
     mpg = mp
     if gate_its != args.steps:
         eng.init_state(seed=rank)
         eng.run(gate_its)
         mpg = eng.map()
-    if engine == "super":
-        flow = np.repeat(np.repeat(mp, 4, axis=0), 4, axis=1)
-        a = aepe(flo, flow, unk, 4)
-    else:
-        a = aepe(flo, mp, unk)
     nodes = eng.M * eng.N
     split = eng.info().split
     dataflow = eng.dataflow()
@@ -516,7 +541,6 @@ def run_engine_config(args, rank, world, local, barrier, engine, names, L, K, ex
             lit = literal_engine_leg(args, rank, opts, I1, I2, flo, unk, gate_its, local)
         except Exception as e:  # reported in the line; the headline value stands
             lit = {"error": f"{type(e).__name__}: {e}"[:300]}
-    Mo, No = I1.shape
     ksuf = {"mixture": 0, "super": 1}[engine]
     R = "double" if args.precision == "fp64" else "float"
     # the padded frame's store (integer frames): binary16 column pairs for
@@ -526,17 +550,16 @@ def run_engine_config(args, rank, world, local, barrier, engine, names, L, K, ex
     vvs = ("VV stored as binary16 column pairs: integer frames" if pair else
            "VV stored as float: integer frames")
     return dict(elapsed=elapsed, kernel_ms=kernel_ms, instrumented_ms=total_ms, pixels=Mo * No, nodes=nodes, aepe=a, name=name,
-                settle=settle, maps_it=maps_it, literal=lit,
+                settle=settle, maps_it=maps_it, literal=lit, outputs=outputs,
                 I1=I1, I2=I2, opts=opts, Mo=Mo, No=No, map=mpg, gate_its=gate_its, map1=mp1, flo=flo, unk=unk, split=split, seed=rank,
                 kernel=(f"gq::k_iter_flow<{R},{vvt},{ksuf},1> (dataflow launch: one per 50-iteration chunk, the "
                         f"per-iteration average; {vvs})" if dataflow else
                         f"gq::k_iter<{R},{vvt},{ksuf},Q> ({vvs})"),
-                dataflow=dataflow,
-                workload=f"{label}: {name} {No}x{Mo} {engine} L={L} K={K} its={args.steps} "
-                         f"(one step = one full-frame iteration)")
+                dataflow=dataflow, workload=workload)
 
 
 TRACK_ITS = 60  # iterations of the per-iteration divergence record (parity gate)
+STATE_PLANES = ("muu", "muv", "sigu", "sigv", "pn", "rou", "w", "alpha")
 
 
 def literal_engine_leg(args, rank, opts, I1, I2, flo, unk, gate_its, device):
@@ -608,7 +631,7 @@ def run_c3(args, rank, world, local, barrier):
     # frames (the level's warped I1 and I2) and options in a single-level
     # context, every launch bracketed by HIP events (gqmap_run_timed)
     dom = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from gqmap_opticalflow_amd import Engine
         with Engine(opts, top["I1w"], top["I2"], "ctf", args.precision, device=local) as e:
             e.init_state(seed=rank + len(C3_SCALES) - 1)
@@ -621,6 +644,7 @@ def run_c3(args, rank, world, local, barrier):
     Mo, No = I1.shape
     return dict(elapsed=elapsed, pix_its=px, aepe=a, name=name, I1=I1, I2=I2, opts=dict(opts, engine="ctf"),
                 Mo=Mo, No=No, its=its, flo=flo, unk=unk, seed=rank, dominant=dom,
+                outputs=dict(flow=flow, its=np.asarray(its, dtype=np.float64)) if args.dump_outputs else None,
                 workload=f"C3: {name} {No}x{Mo} coarse-to-fine, 5 levels 1/16..1 (30x40..480x640), "
                          f"gqmap_ctf K=11, {args.steps} its/level, device imresize/interp2/fillmissing; "
                          f"value counts sum over levels of level pixels x its")
@@ -691,25 +715,31 @@ def run_c1(args, rank, world, local, barrier):
     torch.cuda.synchronize(dev)
     barrier()
     t0 = time.perf_counter()
-    mu_d, _, _, tr = gqmap_cpu_device(o, flo_d, seed=0, return_trace=True)
+    mu_d, sg_d, rou_d, tr = gqmap_cpu_device(o, flo_d, seed=0, return_trace=True)
     torch.cuda.synchronize(dev)
     barrier()
     elapsed = time.perf_counter() - t0
     mu = np.asfortranarray(mu_d.cpu().numpy())
-    # the host-array call (copies included), same seed: bit-identical result
-    gqmap_cpu(o, flo, seed=1, device=local)
-    t1 = time.perf_counter()
-    mu_h = gqmap_cpu(o, flo, seed=0, device=local)[0]
-    host_s = time.perf_counter() - t1
+    outputs = None
+    if args.dump_outputs:
+        host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        outputs = dict(mu=mu, sigma=host(sg_d), rou=host(rou_d), trace=host(tr))
+    host_arrays = None
+    if args.full:
+        # the host-array call (copies included), same seed: bit-identical result
+        gqmap_cpu(o, flo, seed=1, device=local)
+        t1 = time.perf_counter()
+        mu_h = gqmap_cpu(o, flo, seed=0, device=local)[0]
+        host_s = time.perf_counter() - t1
+        host_arrays = {"value": flo.shape[0] * flo.shape[1] * tr.shape[0] / host_s / 1e9, "unit": "Gpixel-iter/s",
+                       "ms_per_step": host_s / tr.shape[0] * 1e3,
+                       "same_bits": bool(np.array_equal(mu_h, mu)),
+                       "note": "gqmap_cpu_run on host arrays: the call's wall clock including the pageable "
+                               "host<->device copies (PCIe-inclusive rate; not the value)"}
     M, N, _ = flo.shape
     err = float(np.sqrt(((mu - flo) ** 2).sum(axis=2))[~unk].mean())
     return dict(elapsed=elapsed, pixels=M * N, nodes=M * N, aepe=err, flow=flo, unk=unk, mu=mu, opts=o, Mo=M, No=N,
-                its=tr.shape[0], settle=settle,
-                host_arrays={"value": M * N * tr.shape[0] / host_s / 1e9, "unit": "Gpixel-iter/s",
-                             "ms_per_step": host_s / tr.shape[0] * 1e3,
-                             "same_bits": bool(np.array_equal(mu_h, mu)),
-                             "note": "gqmap_cpu_run on host arrays: the call's wall clock including the pageable "
-                                     "host<->device copies (PCIe-inclusive rate; not the value)"},
+                its=tr.shape[0], settle=settle, outputs=outputs, host_arrays=host_arrays,
                 workload=f"C1: {name} {N}x{M} legacy/gqmap_cpu.m flow denoising (input = GT flow, unknowns 0), "
                          f"K=9, var=gama=1, dta=inf, {args.steps} its, sigma0 = U+2 (seed 0); flow resident in "
                          f"HBM (gqmap_cpu_run_device); aepe = mean |mu - flow|",
@@ -851,14 +881,19 @@ def tiled_solve(args, rank, world, local, barrier, dist, I1, I2, flo, unk, opts,
             raise RuntimeError(f"rank {rank}: solver stopped after {done}/{args.steps} iterations")
         mp = eng.map()
         col0, col1 = eng.col0, eng.col1
-        # k_iter durations: a replay of the same iterations with HIP events
-        # around every iteration's k_iter launch over the strip
-        eng.init_state(seed=0)
-        done2, total_ms, kernel_ms = eng.run_timed(args.steps)
-        if done2 != args.steps or not np.array_equal(eng.map(), mp):
-            raise RuntimeError(f"rank {rank}: the instrumented replay differs from the timed run")
+        outputs = None
+        if args.dump_outputs:  # this rank's strip of the flow, and the trace
+            outputs = dict(trace=tr, map=mp[:, col0:col1])
+        kernel_ms = 0.0
+        if args.full:
+            # k_iter durations: a replay of the same iterations with HIP events
+            # around every iteration's k_iter launch over the strip
+            eng.init_state(seed=0)
+            done2, total_ms, kernel_ms = eng.run_timed(args.steps)
+            if done2 != args.steps or not np.array_equal(eng.map(), mp):
+                raise RuntimeError(f"rank {rank}: the instrumented replay differs from the timed run")
         sp = None
-        if validate:
+        if validate and args.full:
             # the strips' final state (the replay ends where the timed run
             # did: checked above) against a whole-grid solve on rank 0
             st = eng.get_state()
@@ -881,7 +916,7 @@ def tiled_solve(args, rank, world, local, barrier, dist, I1, I2, flo, unk, opts,
     f[unk] = 0
     e = np.sqrt(((flo[sl] - f[sl]) ** 2).sum(axis=2))
     return dict(elapsed=elapsed, kernel_ms=kernel_ms, pixels=Mo * No, nodes=Mo * (col1 - col0), settle=settle,
-                err_sum=float(e.sum()), err_n=int(e.size), split=opts["split"], strip_parity=sp)
+                outputs=outputs, err_sum=float(e.sum()), err_n=int(e.size), split=opts["split"], strip_parity=sp)
 
 
 def run_tiled(args, rank, world, local, barrier, dist, names, scale, label):
@@ -906,6 +941,8 @@ def run_tiled(args, rank, world, local, barrier, dist, names, scale, label):
             tot[k] += r[k]
         tot["split"] = r["split"]
         tot.setdefault("settle", r.get("settle"))
+        if r["outputs"] is not None:
+            tot.setdefault("outputs", {}).update({f"{name}_{k}": v for k, v in r["outputs"].items()})
         tot["pix_its"] += Mo * No * args.steps
         per_pair.append(dict(name=name, size=f"{No}x{Mo}", err_sum=r["err_sum"], err_n=r["err_n"],
                              elapsed=r["elapsed"]))
@@ -923,6 +960,35 @@ def run_tiled(args, rank, world, local, barrier, dist, names, scale, label):
                            f"its={args.steps} per pair, pairs run in turn")
 
 
+DUMP_LIMIT = 60 << 20  # bytes of array data per --dump-outputs (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path: str, outputs: dict, limit: int = DUMP_LIMIT):
+    """--dump-outputs: every array the timed call returned as path/<name>.npy
+    (float64; float32 arrays stay float32).  Past `limit` bytes in all, the
+    arrays larger than limit/1024 bytes (the small ones stay whole) keep the
+    same fraction of their elements each: a sorted sample of the flattened
+    (C-order) indices drawn without replacement from np.random.default_rng(0),
+    the same for the same shapes from run to run.  Returns the record the
+    line carries."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.asarray(v) for k, v in outputs.items()}
+    arrs = {k: a if a.dtype == np.float32 else a.astype(np.float64) for k, a in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    small = sum(a.nbytes for a in arrs.values() if a.nbytes <= limit // 1024)
+    frac = 1.0 if total <= limit else (limit - small) / (total - small)
+    rng = np.random.default_rng(0)
+    rec = {}
+    for k in sorted(arrs):
+        a = arrs[k]
+        if frac < 1.0 and a.nbytes > limit // 1024:
+            idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * frac)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        rec[k] = {"shape": list(arrs[k].shape), "dtype": str(a.dtype), "saved": int(a.size)}
+    return {"dir": path, "sampled": frac < 1.0, "arrays": rec}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -930,13 +996,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--precision", default="fp64", choices=("fp64", "fp32"))
     ap.add_argument("--config", default="c2", choices=("c1", "c2", "c3", "c4", "c5"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also run everything else the line can carry: the "
+                         "instrumented replay (roofline), the parity gate, the literal-order engine, "
+                         "the strong-scaling leg and strip check, the host-array call (c1) and the CPU baseline; "
+                         "the --no-* options below select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what their call returned (trace, MAP flow, state; rank 0's) "
+                         "as DIR/<name>.npy, float64, at most 64 MB in all (a fixed seeded sample of larger "
+                         "outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-settle", action="store_true",
                     help="time the steps without settling the GPU clocks first (settle_clocks)")
     ap.add_argument("--no-strong-scaling", action="store_true",
                     help="c2: skip the strong-scaling leg (the pair split over the ranks)")
     ap.add_argument("--parity-steps", type=int, default=0,
-                    help="iterations of the parity gate (default: all timed steps; C4: 20)")
+                    help="iterations of the parity gate (default: the timed steps, at most 500; C4: 20)")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the parity gate (CPU model + literal restatement of the same steps, AEPE and "
                          "colour deltas) after the timed region")
@@ -1059,7 +1134,8 @@ def main():
                 cs = r["settle"]["cold_start_ms_per_step"]
                 out["clock_settle"]["cold_start_value"] = units / (cs * 1e-3 * args.steps) / 1e9
         if cfg == "c1":
-            out["host_arrays"] = r["host_arrays"]
+            if r["host_arrays"] is not None:
+                out["host_arrays"] = r["host_arrays"]
             out["value_definition"] = r["value_definition"]
             # per pixel: node 2 x K x 6 flop, edges 4 x K^2 x ~40 flop (legacy/gqmap_cpu.m:20-54)
             fl = (2 * K * 6 + 4 * K * K * 40) * r["pixels"] * r["its"]
@@ -1091,7 +1167,8 @@ def main():
                                         "context on the level's own frames (the pipeline's warped I1 and I2)")
                 out["roofline"]["dominant_level"] = dl
             out["config"]["its_per_level"] = r["its"]
-        else:
+        elif args.full:
+            # from the instrumented replay's kernel mean (a run of its own);
             # tiled: the kernel mean over all pairs' launches; nodes = the
             # rank's average share of a pair's grid
             nsteps = args.steps * (len(r["per_pair"]) if tiled else 1)
@@ -1123,6 +1200,13 @@ def main():
             printed.append(1)
             print(json.dumps(out), flush=True)
 
+    if rank == 0 and args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, r.get("outputs") or {})
+    if not args.full:  # the headline figure alone: everything below is behind --full
+        emit()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     if cfg == "c2" and not tiled and not args.no_strong_scaling:
         # the headline pair split over the ranks (strong scaling).  A watchdog
         # keeps a stuck exchange from costing the whole line: after its limit

@@ -8,5 +8,5 @@ for r in 1 2; do
   done
 done
 for v in cur park; do
-  echo "c3 $v"; GQMAP_LIB=$L/libgqmap_$v.so timeout -k 10 200 python bench.py --config c3 --no-cpu-baseline | grep -o '"value": [0-9.]*' || exit 1
+  echo "c3 $v"; GQMAP_LIB=$L/libgqmap_$v.so timeout -k 10 200 python bench.py --full --config c3 --no-cpu-baseline | grep -o '"value": [0-9.]*' || exit 1
 done
