@@ -107,6 +107,21 @@ constexpr int TS = TAB_STRIDE;
 constexpr int NPLANES = 9;
 constexpr int TRACE_CAP = 8192;
 constexpr int GRAPH_CHUNK = 50;
+// Iterations per launch of a dataflow context (k_iter_flow; chunk_len).  Apart
+// from GRAPH_CHUNK, which also sizes the RCCL sequence buffers and the
+// per-launch graphs.  A launch boundary costs ~70 us on C2: 24-29 us inside
+// the launch (snapshot, lockstep start, drain of the last iterations: the
+// intercept of t(n), profiles/flow_launch_fixed_cost.txt) and ~40 us between
+// two replayed graphs, which only the wall clock sees (chunks of 50 against
+// 250: 131.4 -> 130.3 us per iteration, profiles/flow_groups_chunk_ab.txt).
+// 250 is the smallest launch of the fit at which that is under 0.5% of the
+// launch.  A failed launch is re-run from its snapshot with one launch per
+// iteration, so up to FLOW_CHUNK iterations are repeated.
+#ifndef GQ_FLOW_CHUNK
+#define GQ_FLOW_CHUNK 250
+#endif
+constexpr int FLOW_CHUNK = GQ_FLOW_CHUNK;
+static_assert(FLOW_CHUNK >= 1 && FLOW_CHUNK <= TRACE_CAP, "a launch's trace rows fit the ring");
 constexpr int NFIX = 5;        // fixed slots per block: Energy, sum|dmu_u|, sum|dsig_u|, #nonfinite, AEPE sum
 constexpr int ACC_SLICES = 8;
 constexpr int TRACE_W = 4;     // trace ring columns: Energy, ptdmu, ptdsigma, AEPE (NaN without a truth)
@@ -233,6 +248,15 @@ __device__ __forceinline__ fix128 wave_sum_fix(fix128 v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += shfl_xor_fix(v, o);
     return v;
+}
+// The wave's sum of a small count per lane (0 <= v < 64), bit plane by bit
+// plane on the scalar unit: no cross-lane traffic and no vector registers.
+__device__ __forceinline__ int wave_sum_small(int v)
+{
+    int s = 0;
+#pragma unroll
+    for (int b = 0; b < 6; ++b) s += __popcll(__ballot((v >> b) & 1)) << b;
+    return s;
 }
 __device__ __forceinline__ bool finite_d(double x) { return (bits_of(x) & 0x7ff0000000000000ULL) != 0x7ff0000000000000ULL; }
 
@@ -832,13 +856,24 @@ __device__ __forceinline__ void tile_totals_tail(const FinParams &F, int total, 
 // LIT: the literal-order arithmetic of gqmap_math.h (lit_node_grad /
 // lit_edge_grad; fp64 single-scale mixture engine, Q = 1) in place of the fast
 // specification's node_sums / edge_sums; everything around it is shared.
+// GRP (the dataflow kernel at Q = 1): every wave takes its own tile -- `tile`
+// is then the calling wave's (wave-uniform; < 0: the wave idles) -- and
+// covers grows node rows of it, its lanes row-fastest over grows x 64 / grows
+// nodes.  grows = TM is the plain form (the four waves share one tile, a
+// quarter of its columns each); a group of partial tiles of the last tile
+// row (grouped: grows = its valid node rows <= 4) has a whole tile per wave.
+// The LDS shares keep their size: wave w owns entries [64 w, 64 w + 64) with
+// row stride grows (the plain form's layout at grows = TM), and every wave
+// of a group runs its tile's halo job itself (5 jobs per wave).
 template <typename R, typename VT, int ENG, int Q, bool EDGE_FIRST, bool COH = false, bool NT = false,
-          bool LIT = false>
+          bool LIT = false, bool GRP = false>
 __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, int it, int parity,
                                           int part_r, TileLdsQ<R, Q> &lds, int l0, int l1, double Tcur,
-                                          bool tab_ready, unsigned long long *acc_ring = nullptr)
+                                          bool tab_ready, unsigned long long *acc_ring = nullptr,
+                                          int grows = 0, bool grouped = false)
 {
     static_assert(!LIT || (ENG == 0 && Q == 1 && sizeof(R) == 8), "literal order: fp64 mixture, Q = 1");
+    static_assert(!GRP || (Q == 1 && !LIT), "a tile per wave: one lane per node");
     constexpr bool RS = Q == 0;                       // role split (node / edge waves)
     constexpr int QA = arith_q(Q);                    // lanes per node of the arithmetic
     constexpr int TPIX = tile_pix(Q);                 // nodes per tile
@@ -857,12 +892,17 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
     const int rtid = RS ? tid % TPIX : tid;
     const bool do_node = !RS || tid < TPIX, do_edge = !RS || tid >= TPIX;
     const int pix = rtid / QA, kj = rtid % QA;  // node within the tile, lane within the node
-    const int lm = pix % TM, ln = pix / TM;
+    int lm = pix % TM, ln = pix / TM;
+    if constexpr (GRP) {  // (pix = 64 wave + lane is the node's LDS entry in either form)
+        lm = (tid & 63) % grows;
+        ln = (grouped ? 0 : (tid >> 6) * (64 / TM)) + (tid & 63) / grows;
+    }
     const int m0 = tm * TM, n0 = tn * TN;
     const int m = m0 + lm, n = n0 + ln;
     const int M = P.M, N = P.N;
     const int64_t MNL = P.MNL, MN = (int64_t)M * N;
-    const bool valid = m < M && n < N;
+    bool valid = m < M && n < N;
+    if constexpr (GRP) valid = valid && tile >= 0 && ln < TN;
     const bool inner = valid && node_interior(P, m, n);
     const bool lead = kj == 0;  // the lane that owns the node's outputs
     const int K2 = P.K2;
@@ -888,7 +928,13 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
     const int wave = tid >> 6, lane = tid & 63;
     // halo: 2*(TN+TM) edges (top row and left column, u and v) x Q lanes
     constexpr int HALO_LANES = 2 * (TN + TM) * QA;
-    const bool halo_lane = rtid < HALO_LANES;
+    static_assert(!GRP || HALO_LANES == 64, "a group's waves each run a halo job");
+    bool halo_lane = rtid < HALO_LANES;
+    int htid = rtid;  // the halo edge a lane computes
+    if constexpr (GRP) {
+        if (grouped) halo_lane = tile >= 0;
+        htid = lane;
+    }
 
     for (int l = l0; l < l1; ++l) {
         // (COH: the dataflow kernel, whose alpha a finalize on another XCD
@@ -962,7 +1008,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         // job e+1's operands before computing job e
         constexpr bool PREFETCH = QA >= GQ_PREFETCH_MIN_Q;
         auto job_at = [&](int e) {
-            return edge_job<R, VT, QA, TM, TN, COH>(P, src, e, rtid, m, n, m0, n0, MN * l, inner, valid, mu_u, mu_v,
+            return edge_job<R, VT, QA, TM, TN, COH>(P, src, e, htid, m, n, m0, n0, MN * l, inner, valid, mu_u, mu_v,
                                                 sg_u, sg_v);
         };
         EdgeJob<R> next{};
@@ -1014,8 +1060,19 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
                 eE = eE + g.E;
                 eda = eda + g.da;
                 // neighbour share: (m+1,n) reads in_up, (m,n+1) reads in_left
+                if constexpr (GRP) {
+                    // the shares' row stride is the wave's row count (a lane past the
+                    // tile's columns stays out of the next wave's entries)
+                    if (dir == 0 && lm + 1 < grows && ln < TN) { in_up[uv][0][pix + 1] = g.du2; in_up[uv][1][pix + 1] = g.do2; }
+                    if (dir == 1 && ln + 1 < TN) { in_left[uv][0][pix + grows] = g.du2; in_left[uv][1][pix + grows] = g.do2; }
+                } else {
                 if (lead && dir == 0 && lm + 1 < TM) { in_up[uv][0][pix + 1] = g.du2; in_up[uv][1][pix + 1] = g.do2; }
                 if (lead && dir == 1 && ln + 1 < TN) { in_left[uv][0][pix + TM] = g.du2; in_left[uv][1][pix + TM] = g.do2; }
+                }
+            } else if constexpr (GRP) {  // a group's wave fills its own 64 entries, hr < its rows on the left
+                const int hb = grouped ? wave * 64 : 0;
+                if (dir == 0) { in_up[uv][0][hb + hr * grows] = g.du2; in_up[uv][1][hb + hr * grows] = g.do2; }
+                else if (hr < grows) { in_left[uv][0][hb + hr] = g.du2; in_left[uv][1][hb + hr] = g.do2; }
             } else if (rtid % QA == 0) {
                 if (dir == 0) { in_up[uv][0][hr * TM] = g.du2; in_up[uv][1][hr * TM] = g.do2; }
                 else          { in_left[uv][0][hr] = g.du2; in_left[uv][1][hr] = g.do2; }
@@ -1052,7 +1109,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
     fE = wave_sum_fix(fE);
     fmu = wave_sum_fix(fmu);
     fsg = wave_sum_fix(fsg);
-    fix128 fnf = wave_sum_fix((fix128)nonfinite);
+    const fix128 fnf = (fix128)wave_sum_small(nonfinite);  // (at most 4 per component and lane: <= 32)
     if (ENG == 2) fae = wave_sum_fix(fae);
     if (lane == 0) {
         red[0][wave] = fE;
@@ -1579,10 +1636,23 @@ __global__ __launch_bounds__(256) void k_persist_snap(const Ctl *ctl, const unsi
 // of iteration j leaves idle: a launch per iteration pays for its busiest
 // CU's tile count (C2: 925 tiles on 768 resident slots).
 //
-// Deadlock-free without co-residency: an item is claimed only by a running
-// workgroup, which holds it until done, and waits only for items earlier in
-// its own queue's order or of the previous iteration in a neighbouring band;
-// the earliest unfinished item therefore always has its inputs.  Spins are
+// Deadlock-free without co-residency of the whole grid: an item is claimed
+// only by a running workgroup, which holds it until done, and waits only for
+// items earlier in its own queue's order or of the previous iteration in a
+// neighbouring band.  Take the unfinished items of the lowest iteration j:
+// each queue hands its items out in order, so the first unfinished item of
+// every queue that still has one of iteration j is claimed as soon as that
+// queue has a running workgroup free, and all it waits for is of iteration
+// j - 1 (finished) or the finalize of j - 2 (every item of j - 2 has
+// arrived).  The progress condition is therefore one running workgroup per
+// XCD queue (the grid is at least 8 workgroups, blockIdx & 7 the queue), not
+// a resident grid.  A group of partial tiles (GQ_FLOW_GROUPS) is one queue
+// item holding up to four tiles that follow each other in the band's walk:
+// it waits for the union of its members' dependencies -- members' own and
+// their neighbours' iteration j - 1, all of them earlier in the same queue's
+// order (a group never crosses a band) or in a neighbouring band -- and
+// publishes all its members together, so the argument holds with "item"
+// read as "group".  Spins are
 // still bounded: a timeout raises the persistent path's failure word
 // (BAR_FAIL), every workgroup leaves, and the host restores the chunk's
 // snapshot and goes on with one launch per iteration (persist_recover).
@@ -1638,19 +1708,27 @@ static_assert((FL_ACC & 1) == 0, "u64 alignment of the accumulator slots");
 // super engine's mixture components are separate items, L > 1).  fin_need:
 // the finalized count item j needs -- j - 1 normally (iterations up to
 // j - 2), j when finalize(j - 1) updated alpha (L > 1 past alpha_start).
+// A group of tiles (grp: its 4 member tiles, < 0 past its size; else
+// nullptr): lanes 0-4 wait for member 0 and its neighbours as for a single
+// tile, lanes 16 + 5 (k - 1) .. + 4 for member k = 1..3.
 __device__ __forceinline__ int flow_wait(unsigned *fl, unsigned *bar, int tiles_m, int ntiles, int tile, int l,
-                                         int L, int j, int fin_need, int *sh)
+                                         int L, int j, int fin_need, int *sh, const int *grp = nullptr)
 {
     if (threadIdx.x < 64) {
         const int x = threadIdx.x;
+        int d = x;  // the dependency lane (0: the tile itself, 1-4: above, below, left, right)
+        if (grp && x >= 16 && x < 31) {
+            tile = grp[1 + (x - 16) / 5];
+            d = (x - 16) % 5;
+        }
         const int tm = tile % tiles_m;
         int dep = -1;  // the tile whose iteration j - 1 this lane waits for
-        if (j > 0) {
-            if (x == 0) dep = tile;
-            else if (x == 1 && tm > 0) dep = tile - 1;
-            else if (x == 2 && tm < tiles_m - 1 && tile + 1 < ntiles) dep = tile + 1;
-            else if (x == 3 && tile >= tiles_m) dep = tile - tiles_m;
-            else if (x == 4 && tile + tiles_m < ntiles) dep = tile + tiles_m;
+        if (j > 0 && tile >= 0) {
+            if (d == 0) dep = tile;
+            else if (d == 1 && tm > 0) dep = tile - 1;
+            else if (d == 2 && tm < tiles_m - 1 && tile + 1 < ntiles) dep = tile + 1;
+            else if (d == 3 && tile >= tiles_m) dep = tile - tiles_m;
+            else if (d == 4 && tile + tiles_m < ntiles) dep = tile + tiles_m;
         }
         if (dep >= 0) dep = dep * L + l;
         unsigned spins = 0;
@@ -1781,6 +1859,15 @@ __device__ unsigned long long g_flow_tl[FLOW_TL_WORDS];
 #ifndef GQ_FLOW_ROWS
 #define GQ_FLOW_ROWS 1
 #endif
+// Partial tiles of the last tile row grouped by up to four into one item, a
+// tile per wave (k_iter_flow, iter_tile's GRP form).  C2's 388 node rows
+// leave a 25th tile row of 4: its 37 tiles held a slot for a full item time
+// each with 16 of 64 lanes live; grouped they are 13 items (a group stays
+// inside its band: 8 groups of four and 5 single tiles), 925 -> 901 items
+// per iteration (profiles/flow_groups_chunk_ab.txt: -2.2 to -2.6%).
+#ifndef GQ_FLOW_GROUPS
+#define GQ_FLOW_GROUPS 1
+#endif
 // W > 0: the waves per SIMD, overriding the defaults above (the large-frame
 // instantiation, launch_flow_q)
 template <typename R, typename VT, int ENG, int Q, bool LIT = false, int W = 0>
@@ -1805,7 +1892,17 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     // items per tile and iteration: one per mixture component for the super
     // engine (its node grid is small; a tile's components run back to back
     // in the queue), one otherwise (L = 1)
-    const int L = ENG == 1 ? P.L : 1, nbl = nb * L, nitems = ntiles * L;
+    const int L = ENG == 1 ? P.L : 1, nitems = ntiles * L;
+    // Groups (GQ_FLOW_GROUPS; the fast arithmetic at one lane per node): when
+    // the last tile row holds vr <= 4 node rows, a tile's valid nodes fit in
+    // one wave, and up to four of its tiles that follow each other in the
+    // band's row walk -- the band's nlast last positions -- are one item:
+    // wave w runs member w.  nbl: the band's items per iteration.
+    constexpr bool GRP = GQ_FLOW_GROUPS && Q == 1 && !LIT && (ENG == 0 || ENG == 2);
+    const int vr = P.M - (P.tiles_m - 1) * tile_rows(Q);
+    const bool groups = GRP && GQ_FLOW_ROWS && vr <= 4;
+    const int nlast = groups ? (s0 + nb) / P.tiles_m - s0 / P.tiles_m : 0;  // the band's tiles in the last tile row
+    const int nbl = groups ? nb - nlast + ((nlast + 3) >> 2) : nb * L;
     constexpr int INV = ENG == 2 && Q == 1 ? GQ_PHASE_MIX_CTF_Q1_INV : GQ_PHASE_MIX_OTHER_INV;
     // (the phase mix: the fast mixture engine; the literal kernel's with
     // GQ_FLOW_LIT_MIX -- its second instantiation spilled at 3 waves)
@@ -1813,6 +1910,7 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     const bool edge_first = MIX && ((((b >> 3) / P.cu_slots) & 1) != INV);
     __shared__ TileLdsQ<R, Q> lds;
     __shared__ int sh_i, sh_go, sh_last;
+    __shared__ int sh_grp[4];  // GRP: the item's tiles (< 0 past a group's size)
     __shared__ double tot[NFIX + GQMAP_LMAX];
     __shared__ unsigned long long sh_acc[4 * (NFIX + GQMAP_LMAX)];
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(fl + FL_ACC);
@@ -1833,31 +1931,55 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
             }
         }
         __syncthreads();
-        const int i = sh_i, j = i / nbl, pos = (i % nbl) / L, l = ENG == 1 ? i % L : 0;
+        const int i = sh_i, j = i / nbl, l = ENG == 1 ? i % L : 0;
         if (j >= n_iter) break;
+        int pos = (i % nbl) / L, gsize = 1;  // the item's first walk position and its tiles
+        const bool grouped = groups && pos >= nb - nlast;
+        if (grouped) {
+            pos = nb - nlast + 4 * (pos - (nb - nlast));
+            gsize = min(4, nb - pos);
+        }
         const int tile = GQ_FLOW_ROWS ? band_row_tile(pos, s0, s0 + nb, P.tiles_m) : s0 + pos;
+        if constexpr (GRP) {  // the member tiles (the previous item's readers are past its last barrier)
+            if (threadIdx.x < 4)
+                sh_grp[threadIdx.x] = threadIdx.x == 0 ? tile
+                                      : (int)threadIdx.x < gsize ? band_row_tile(pos + threadIdx.x, s0, s0 + nb, P.tiles_m) : -1;
+            __syncthreads();
+        }
         const int it = it0 + j, parity = (done0 + j) & 1;
         // finalize(j - 1) changed alpha (fin_apply: it - 1 > alpha_start, L > 1)
         const bool alpha_moved = P.L > 1 && it - 1 > P.fin.alpha_start;
 #if GQ_FLOW_TL
         const unsigned long long tl_claim = __builtin_amdgcn_s_memrealtime();
 #endif
-        if (!flow_wait(fl, bar, P.tiles_m, ntiles, tile, l, L, j, alpha_moved ? j : j - GQ_FLOW_LAG + 1, &sh_go)) break;
+        if (!flow_wait(fl, bar, P.tiles_m, ntiles, tile, l, L, j, alpha_moved ? j : j - GQ_FLOW_LAG + 1, &sh_go,
+                       GRP && grouped ? sh_grp : nullptr))
+            break;
         if (GQ_FLOW_LAG > 2 && threadIdx.x == 0)  // (for the overshoot check at the exit)
             __hip_atomic_fetch_max(fl + FL_MAXJ, (unsigned)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #if GQ_FLOW_TL
         const unsigned long long tl_go = __builtin_amdgcn_s_memrealtime();
 #endif
-        double T = T0;  // fin_apply's temperature decay after each earlier iteration
-        if (P.fin.t_decay_every > 0)
-            for (int q = it0; q < it; ++q)
-                if (q % P.fin.t_decay_every == 0) T = fmax(T * P.fin.drate, P.fin.t_min);
+        // fin_apply's temperature decay after each earlier iteration of the
+        // launch: one step per decay (the iterations q in [it0, it) with
+        // q % t_decay_every == 0), the same sequence of roundings
+        double T = T0;
+        if (P.fin.t_decay_every > 0) {
+            const int e = P.fin.t_decay_every;
+            const int nd = (it + e - 1) / e - (it0 + e - 1) / e;  // (it0 >= 0)
+            for (int q = 0; q < nd; ++q) T = fmax(T * P.fin.drate, P.fin.t_min);
+        }
         unsigned long long *slot = acc + (size_t)(j % FL_SLOTS) * FL_ACC_SLOT;
         const int l0 = ENG == 1 ? l : 0, l1 = ENG == 1 ? l + 1 : 1;  // (L = 1 unless super)
+        // GRP: the calling wave's tile -- the item's own, or its member of a group
+        const int wtile = GRP ? __builtin_amdgcn_readfirstlane(grouped ? sh_grp[threadIdx.x >> 6] : tile) : tile;
+        const int wrows = grouped ? vr : tile_rows(Q);
         if (MIX && edge_first)
-            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT>(P, tile, it, parity, 0, lds, l0, l1, T, false, slot);
+            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+                                                                          wrows, grouped);
         else
-            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT>(P, tile, it, parity, 0, lds, l0, l1, T, false, slot);
+            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+                                                                           wrows, grouped);
         // publish: every wave's stores (state, rou, the slot's sums) are done
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -1872,12 +1994,15 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
                    (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
         }
 #endif
+        // (a group: every member tile's count, and as many arrival tickets)
+        if (GRP && grouped && threadIdx.x > 0 && (int)threadIdx.x < gsize)
+            __hip_atomic_store(fl + FL_DONE + sh_grp[threadIdx.x], (unsigned)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (threadIdx.x == 0) {
             __hip_atomic_store(fl + FL_DONE + tile * L + l, (unsigned)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned tk = __hip_atomic_fetch_add(fl + FL_ARR + (j % FL_SLOTS) * FL_LINE, 1u, __ATOMIC_RELAXED,
+            const unsigned tk = __hip_atomic_fetch_add(fl + FL_ARR + (j % FL_SLOTS) * FL_LINE, (unsigned)gsize, __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_AGENT);
             if (GQ_FLOW_PAIR) sh_i = (int)__hip_atomic_fetch_add(q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sh_last = tk == (unsigned)(nitems - 1);
+            sh_last = tk == (unsigned)(nitems - gsize);
         }
         have = true;
         __syncthreads();
@@ -2288,6 +2413,7 @@ struct gqmap_ctx {
     gq::Policy pol = gq::g_pol;  // execution policies, fixed at creation
     unsigned *d_flow = nullptr;  // k_iter_flow queue state (flow_words(tiles) words, zero between launches)
     int flow_n = 0;
+    int graph_n = 0;  // iterations of the chunk graph (chunk_len at its capture)
 };
 
 
@@ -3516,7 +3642,19 @@ gqmap_status capture_steps(gqmap_ctx *c, int n, hipGraphExec_t *out)
     return GQMAP_OK;
 }
 
-gqmap_status ensure_graph(gqmap_ctx *c) { return capture_steps(c, GRAPH_CHUNK, &c->graph); }
+// Iterations of the replayed chunk graph: FLOW_CHUNK when the dataflow launch
+// takes the context (one launch per chunk), else GRAPH_CHUNK.  (A context
+// that falls back to one launch per iteration -- persist_recover -- drops
+// its graph, and the next one is captured at GRAPH_CHUNK.)
+int chunk_len(gqmap_ctx *c) { return launch_flow(c, 1, true) ? FLOW_CHUNK : GRAPH_CHUNK; }
+
+gqmap_status ensure_graph(gqmap_ctx *c)
+{
+    const int n = chunk_len(c);
+    if (c->graph && c->graph_n != n) drop_graph(c);
+    c->graph_n = n;
+    return capture_steps(c, n, &c->graph);
+}
 
 // A loopback-transport tile (tests) runs its launches directly: its
 // collectives are host barriers and cross-stream event waits between the
@@ -4114,12 +4252,14 @@ gqmap_status gqmap_run_aepe(gqmap_ctx *c, int n_iter, int *n_done, double *trace
         int left = chunk;
         c->ctl_known = false;
         if (c->pol.graph && !loop_comm(c)) {
-            // GRAPH_CHUNK-iteration graphs, then the remainder as graphs of
-            // 2^k iterations (a short run replays graphs too)
-            if (left >= GRAPH_CHUNK && (s = ensure_graph(c)) != GQMAP_OK) return s;
-            while (left >= GRAPH_CHUNK) {
+            // chunk graphs (GRAPH_CHUNK iterations; FLOW_CHUNK as one dataflow
+            // launch), then the remainder as graphs of 2^k iterations (a
+            // short run replays graphs too)
+            const int gc = chunk_len(c);
+            if (left >= gc && (s = ensure_graph(c)) != GQMAP_OK) return s;
+            while (left >= gc) {
                 GQ_HIP(hipGraphLaunch(c->graph, c->stream));
-                left -= GRAPH_CHUNK;
+                left -= gc;
             }
             // (a persistent small-level context or a deferred RCCL strip runs
             // the remainder as ONE launch / one sequence, directly: as 2^k
@@ -4195,11 +4335,11 @@ gqmap_status gqmap_run_timed(gqmap_ctx *c, int n_iter, int *n_done, double *tota
     if (deferred(c)) {  // the production sequences, each iteration's k_iter launch bracketed
         for (int i = 0; i < n_iter; i += GRAPH_CHUNK)
             if ((s = launch_seq_deferred(c, std::min(GRAPH_CHUNK, n_iter - i), &ev[2 + 2 * i])) != GQMAP_OK) return s;
-    } else if (launch_flow(c, n_iter, true)) {  // one pair around each chunk's dataflow launch
+    } else if (launch_flow(c, n_iter, true)) {  // one pair around each chunk's dataflow launch (gqmap_run's launches)
         timed = 0;
-        for (int i = 0; i < n_iter; i += GRAPH_CHUNK, ++timed) {
+        for (int i = 0; i < n_iter; i += FLOW_CHUNK, ++timed) {
             GQ_HIP(hipEventRecord(ev[2 + 2 * timed], c->stream));
-            (void)launch_flow(c, std::min(GRAPH_CHUNK, n_iter - i));
+            (void)launch_flow(c, std::min(FLOW_CHUNK, n_iter - i));
             GQ_HIP(hipEventRecord(ev[3 + 2 * timed], c->stream));
         }
     } else {
@@ -4336,6 +4476,10 @@ int gqmap_debug_flow(gqmap_ctx *c)
     DeviceGuard dg(c->device);
     return launch_flow(c, 1, true) ? 1 : 0;
 }
+
+// Not in the public header (tests, scripts): the iterations a dataflow
+// context runs per launch (FLOW_CHUNK).
+int gqmap_debug_flow_chunk(void) { return FLOW_CHUNK; }
 
 // Not in the public header (tests, A/B scripts): set one execution policy of
 // gq::Policy by name, process-wide; contexts created (or graphs captured)

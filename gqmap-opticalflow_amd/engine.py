@@ -243,7 +243,7 @@ class Engine:
 
     def dataflow(self) -> bool:
         """Whether runs take the dataflow launch (k_iter_flow, one launch per
-        50-iteration chunk) rather than one k_iter launch per iteration
+        chunk of FLOW_CHUNK iterations) rather than one k_iter launch per iteration
         (gqmap_debug_flow; the library's flow policy)."""
         f = self.lib.gqmap_debug_flow
         f.restype = C.c_int
