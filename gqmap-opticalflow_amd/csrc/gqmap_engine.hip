@@ -75,7 +75,64 @@ __device__ __forceinline__ float gq_sqrt_dev(float x)
     const float r = rm <= 0.f ? sm : s;
     return rp > 0.f ? sp : r;
 }
+// gq_sqrt_dev in steps (gqmap_math.h, RootStaged): begin, stage<1..4> and end
+// together are exactly the operations above, in their order.
+template <typename R>
+struct RootStaged;
+template <>
+struct RootStaged<double> {
+    double x, g, h, r, d;
+    __device__ __forceinline__ void begin(double v)
+    {
+        x = v;
+        h = __builtin_amdgcn_rsq(x);
+    }
+    template <int S>
+    __device__ __forceinline__ void stage()
+    {
+        if constexpr (S == 1) {
+            g = x * h;
+            h = 0.5 * h;
+        } else if constexpr (S == 2) {
+            r = fma(-h, g, 0.5);
+            g = fma(g, r, g);
+            h = fma(h, r, h);
+        } else if constexpr (S == 3) {
+            d = fma(-g, g, x);
+            g = fma(d, h, g);
+        } else {
+            d = fma(-g, g, x);
+        }
+    }
+    __device__ __forceinline__ double end() const { return fma(d, h, g); }
+};
+template <>
+struct RootStaged<float> {
+    float x, s, sm, sp, rm, rp, r;
+    __device__ __forceinline__ void begin(float v)
+    {
+        x = v;
+        s = __builtin_amdgcn_sqrtf(x);
+    }
+    template <int S>
+    __device__ __forceinline__ void stage()
+    {
+        if constexpr (S == 1) {
+            const int si = __float_as_int(s);
+            sm = __int_as_float(si - 1);
+            sp = __int_as_float(si + 1);
+        } else if constexpr (S == 2) {
+            rm = fmaf(-sm, s, x);
+        } else if constexpr (S == 3) {
+            rp = fmaf(-sp, s, x);
+        } else {
+            r = rm <= 0.f ? sm : s;
+        }
+    }
+    __device__ __forceinline__ float end() const { return rp > 0.f ? sp : r; }
+};
 }  // namespace gq
+#define GQ_ROOT_STAGED 1
 
 #define GQ_HD __device__ __forceinline__
 #define GQ_SQRT(x) gq::gq_sqrt_dev(x)
@@ -866,7 +923,7 @@ __device__ __forceinline__ void tile_totals_tail(const FinParams &F, int total, 
 // row stride grows (the plain form's layout at grows = TM), and every wave
 // of a group runs its tile's halo job itself (5 jobs per wave).
 template <typename R, typename VT, int ENG, int Q, bool EDGE_FIRST, bool COH = false, bool NT = false,
-          bool LIT = false, bool GRP = false>
+          bool LIT = false, bool GRP = false, int ROTF = GQ_NODE_ROT_OTHER>
 __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, int it, int parity,
                                           int part_r, TileLdsQ<R, Q> &lds, int l0, int l1, double Tcur,
                                           bool tab_ready, unsigned long long *acc_ring = nullptr,
@@ -980,10 +1037,13 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
             // (at one lane per node only with float taps: the fp64-tap Q = 1
             // kernels would cross 168 VGPRs, 3 -> 2 waves per SIMD)
             constexpr bool PF = QA >= GQ_NODE_PF_MIN_Q && (QA > 1 || sizeof(VT) == 4);
-            Sums<R> S = fast ? node_sums<ENG, false, PF>(tab, kj, K2, QA, fv, P.I1, P.Mo, P.No, P.epsn, c, mu_u,
-                                                         mu_v, m, n + P.n_off)
-                             : node_sums<ENG, true, PF>(tab, kj, K2, QA, fv, P.I1, P.Mo, P.No, P.epsn, c, mu_u,
-                                                        mu_v, m, n + P.n_off);
+            // the pipelined loop's form (node_sums ROT: rotation, trips per
+            // pass), chosen by the kernel that instantiates the tile (ROTF)
+            constexpr int ROT = PF ? ROTF : 0;
+            Sums<R> S = fast ? node_sums<ENG, false, PF, ROT>(tab, kj, K2, QA, fv, P.I1, P.Mo, P.No, P.epsn, c, mu_u,
+                                                              mu_v, m, n + P.n_off)
+                             : node_sums<ENG, true, PF, ROT>(tab, kj, K2, QA, fv, P.I1, P.Mo, P.No, P.epsn, c, mu_u,
+                                                             mu_v, m, n + P.n_off);
             if (QA > 1) S = lane_combine<QA>(S);
             nd = node_epi(S, c, P.lamd, P.guard != 0, T, a, sg_u, sg_v, pn, ENG == 2);
             if constexpr (RS) {  // to the edge lane of the same node
@@ -1899,6 +1959,12 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     // band's row walk -- the band's nlast last positions -- are one item:
     // wave w runs member w.  nbl: the band's items per iteration.
     constexpr bool GRP = GQ_FLOW_GROUPS && Q == 1 && !LIT && (ENG == 0 || ENG == 2);
+    // form of the node loop (node_sums ROT): the fp64 mixture item on the
+    // binary16 pair store at its own register allocation (C2's kernel; not
+    // the 3-wave large-frame form, not the float store: not measured)
+    constexpr int ROTF = ENG == 0 && Q == 1 && !LIT && W == 0 && sizeof(R) == 8 && is_vvh2<VT>::value
+                             ? (GQ_NODE_ROT_FLOW_FP64 | NODE_UNROLL(GQ_NODE_UNROLL_FLOW_FP64))
+                             : GQ_NODE_ROT_OTHER;
     const int vr = P.M - (P.tiles_m - 1) * tile_rows(Q);
     const bool groups = GRP && GQ_FLOW_ROWS && vr <= 4;
     const int nlast = groups ? (s0 + nb) / P.tiles_m - s0 / P.tiles_m : 0;  // the band's tiles in the last tile row
@@ -1975,10 +2041,10 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
         const int wtile = GRP ? __builtin_amdgcn_readfirstlane(grouped ? sh_grp[threadIdx.x >> 6] : tile) : tile;
         const int wrows = grouped ? vr : tile_rows(Q);
         if (MIX && edge_first)
-            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP, ROTF>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
                                                                           wrows, grouped);
         else
-            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP, ROTF>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
                                                                            wrows, grouped);
         // publish: every wave's stores (state, rou, the slot's sums) are done
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -322,6 +322,46 @@ GQ_HD R bicubic_taps4(const Taps16<E> &T, R so, R to)
     return fma(s3, v[3], fma(s2, v[2], fma(s1, v[1], s0 * v[0])));
 }
 
+// A square root taken in steps, so a loop can place them between other work
+// (node_sums, rotated form).  The generic form is GQ_SQRT at the end; an
+// includer that defines GQ_ROOT_STAGED provides RootStaged<double> /
+// RootStaged<float> itself, with the operations of its GQ_SQRT split over
+// stage<1..4>() and end() -- the same operations, so the same bits.
+#ifndef GQ_ROOT_STAGED
+template <typename R>
+struct RootStaged {
+    R x;
+    GQ_HD void begin(R v) { x = v; }
+    template <int S>
+    GQ_HD void stage() {}
+    GQ_HD R end() const { return GQ_SQRT(x); }
+};
+#endif
+// bicubic_taps4 with the four column chains advanced together, one tap row
+// per step, and (WITH) one stage of the root rt after each step: every value
+// is computed by bicubic_taps4's operations on its operands.
+template <bool WITH, typename R, typename E, typename RT>
+GQ_HD R bicubic_taps4_staged(const Taps16<E> &T, R so, R to, RT &rt)
+{
+    R t0, t1, t2, t3, s0, s1, s2, s3;
+    keys4(to, t0, t1, t2, t3);
+    keys4(so, s0, s1, s2, s3);
+    auto tap = [&](int c, int r) -> R {
+        if constexpr (is_vvh2<E>::value) return tap_col<R>(T.v[4 * (c >> 1) + r], c & 1);
+        else return R(T.v[4 * c + r]);
+    };
+    R v[4];
+    for (int c = 0; c < 4; ++c) v[c] = tap(c, 0) * t0;
+    if constexpr (WITH) rt.template stage<1>();
+    for (int c = 0; c < 4; ++c) v[c] = fma(tap(c, 1), t1, v[c]);
+    if constexpr (WITH) rt.template stage<2>();
+    for (int c = 0; c < 4; ++c) v[c] = fma(tap(c, 2), t2, v[c]);
+    if constexpr (WITH) rt.template stage<3>();
+    for (int c = 0; c < 4; ++c) v[c] = fma(tap(c, 3), t3, v[c]);
+    if constexpr (WITH) rt.template stage<4>();
+    return fma(s3, v[3], fma(s2, v[2], fma(s1, v[1], s0 * v[0])));
+}
+
 GQ_HD uint32_t cell_elem(int iy, int ix, int M2) { return (uint32_t)(iy - 1) + GQ_UMUL24(M2, ix - 1); }
 
 // Where the bicubic reads the padded frame: cell (iy, ix) (1-based) starts at
@@ -845,7 +885,21 @@ GQ_HD NodeCoef<R> node_coef(R o1, R o2, R p)
 // loaded before sample k's arithmetic, so the gather latency overlaps it
 // (the small-grid kernels run 1-2 waves per SIMD, memory waits dominating);
 // the same operations on the same operands, so the same bits.
-template <int ENG, bool CLAMP = true, bool PF = false, typename R, typename TP, typename TV, typename IP>
+// ROT (with PF; a sum of the bits below): the loop rotated by one stage --
+// the trip that interpolates sample k also takes the root of sample k - dk's
+// fma(d, d, eps), carried in one register, and adds it into the sums, so the
+// root's dependent chain has the interpolation to issue beside; the first
+// sample is peeled in front of the loop and the last root behind it.  The
+// sums are added in increasing k on unchanged operands: the same bits.
+//   NODE_ROT       the rotation itself
+//   NODE_ROT_STAGE the root in stages between the interpolation's tap rows
+//                  (bicubic_taps4_staged)
+// NODE_UNROLL(n), with or without NODE_ROT: n trips per pass of the pipelined
+// loop (the includer's GQ_PAIR_UNROLL_K pragma).
+constexpr int NODE_ROT = 1, NODE_ROT_STAGE = 2, NODE_ROT_FLAGS = 255;
+constexpr int NODE_UNROLL(int n) { return n << 8; }
+constexpr int node_rot_unroll(int rot) { return (rot >> 8) > 1 ? (rot >> 8) : 1; }
+template <int ENG, bool CLAMP = true, bool PF = false, int ROT = 0, typename R, typename TP, typename TV, typename IP>
 GQ_HD Sums<R> node_sums(TP tab, int k0, int K2, int dk, const TV &V, IP I1, int Mo, int No,
                         R eps, const NodeCoef<R> &c, R u1, R u2, int m, int n)
 {
@@ -862,10 +916,48 @@ GQ_HD Sums<R> node_sums(TP tab, int k0, int K2, int dk, const TV &V, IP I1, int 
             else if constexpr (ENG == 2) return cell_ctf4_v<CLAMP>(V, Mo, No, m + 1, n + 1, x1, x2, so, to);
             else return cell4_v<CLAMP>(V, Mo, No, m + 1, n + 1, x1, x2, so, to);
         };
+        if constexpr ((ROT & NODE_ROT_FLAGS) != 0) {
+            static_assert(ROT & NODE_ROT, "the other bits modify the rotated loop");
+            constexpr bool STAGE = (ROT & NODE_ROT_STAGE) != 0;
+            constexpr int UNR = node_rot_unroll(ROT);
+            (void)UNR;  // (an includer without unroll pragmas)
+            if (k0 < K2) {
+                const int klast = k0 + (K2 - 1 - k0) / dk * dk;
+                R so, to;
+                auto T = load_taps16(V.p, locate(k0, so, to), V.ld);
+                RootStaged<R> rt;
+                // sample k: fma(d, d, eps), with the loads of the sample after
+                // it issued first and (with_root) the stages of rt in between
+                auto trip = [&](int k, auto with_root) -> R {
+                    const auto Tk = T;
+                    const R sok = so, tok = to;
+                    const int kn = k + dk <= klast ? k + dk : klast;  // the last pass reloads its own cell
+                    T = load_taps16(V.p, locate(kn, so, to), V.ld);
+                    const R v4 = STAGE ? bicubic_taps4_staged<decltype(with_root)::value, R>(Tk, sok, tok, rt)
+                                       : bicubic_taps4<R>(Tk, sok, tok);
+                    const R d = fma(v4, R(-0.25), I);
+                    return fma(d, d, eps);
+                };
+                R q = trip(k0, std::false_type{});
+                GQ_PAIR_UNROLL_K(UNR)
+                for (int k = k0 + dk; k <= klast; k += dk) {
+                    const R qp = q;  // sample k - dk's
+                    if constexpr (STAGE) rt.begin(qp);
+                    q = trip(k, std::true_type{});
+                    if constexpr (STAGE) S.add(tab, k - dk, rt.end());
+                    else S.add(tab, k - dk, GQ_SQRT(qp));
+                }
+                S.add(tab, klast, GQ_SQRT(q));
+            }
+            return S;
+        }
         if (k0 < K2) {
             const int klast = k0 + (K2 - 1 - k0) / dk * dk;
             R so, to;
             auto T = load_taps16(V.p, locate(k0, so, to), V.ld);
+            constexpr int UNR = node_rot_unroll(ROT);
+            (void)UNR;  // (an includer without unroll pragmas)
+            GQ_PAIR_UNROLL_K(UNR)
             for (int k = k0; k <= klast; k += dk) {
                 const auto Tk = T;
                 const R sok = so, tok = to;

@@ -72,6 +72,21 @@
 #ifndef GQ_NODE_PF_MIN_Q
 #define GQ_NODE_PF_MIN_Q 1
 #endif
+// Form of that loop per instantiation (node_sums ROT).  Trips per loop pass
+// of the fp64 mixture item of the dataflow launch at one lane per node on the
+// binary16 pair store (C2's kernel): 4 (profiles/node_rotate_ab.txt: C2 fp64 -1.3%; 2: -0.9%, 3: -1.2%,
+// 9: -0.6%).  The loop rotated by one stage (a sum of NODE_ROT 1 and
+// NODE_ROT_STAGE 2; same file): 1 is +0.9%, 3 -0.3%, 3 at two trips per pass
+// -0.7% against -0.9% without the rotation -- off everywhere.
+#ifndef GQ_NODE_UNROLL_FLOW_FP64
+#define GQ_NODE_UNROLL_FLOW_FP64 4
+#endif
+#ifndef GQ_NODE_ROT_FLOW_FP64
+#define GQ_NODE_ROT_FLOW_FP64 0
+#endif
+#ifndef GQ_NODE_ROT_OTHER  // every other pipelined loop: per-launch kernels, fp32, Q >= 2, ctf
+#define GQ_NODE_ROT_OTHER 0
+#endif
 #ifndef GQ_UNROLL_MIN_Q
 #define GQ_UNROLL_MIN_Q 2
 #endif
