@@ -798,6 +798,57 @@ __device__ __forceinline__ EdgeJob<R> edge_job(const IterParams<R, VT> &P, const
     return jb;
 }
 
+#ifndef GQ_FLOW_TL  // diagnostic builds: the dataflow launch's timeline (k_iter_flow)
+#define GQ_FLOW_TL 0
+#endif
+
+// The halo chain of the plain dataflow item (iter_tile HALO == 1, DESIGN.md
+// 4): the halo job's pair range in four ascending slices, wave w running
+// slice w for all 64 halo edges (lane = edge) from the six sums wave w - 1
+// left in s[][lane]; flag[w] = the item's token once wave w has stored its
+// sums.  The token grows from item to item of a workgroup (its claim index +
+// 1; the kernel clears the flags once, at its start), so nothing is cleared
+// between items.
+template <typename R>
+struct HaloChain {
+    R s[6][64];
+    unsigned flag[4];
+    unsigned *fail;  // the launch's failure word (a spin that times out raises it)
+};
+constexpr unsigned HALO_SPIN_LIMIT = 1u << 22;  // polls (~0.1 us each) before a hand-over wait gives up
+
+// Wave w > 0 waits for the sums of slice w - 1 (all lanes; wave-uniform).  An
+// acquire load at workgroup scope pairs with halo_chain_pass's release store.
+// Waves only wait for a wave earlier in the chain, and none is at a barrier
+// while it owes a slice, so the wait ends; it is bounded all the same: on a
+// timeout the wave raises the failure word, goes on with whatever the buffer
+// holds and still passes its own flag on (the waves behind it do not wait in
+// turn), and the host discards the launch (persist_recover).
+template <typename R>
+__device__ __forceinline__ Sums<R> halo_chain_take(HaloChain<R> *hc, unsigned tok, int w, int lane)
+{
+    unsigned spins = 0;
+    while (__builtin_amdgcn_readfirstlane(
+               __hip_atomic_load(&hc->flag[w - 1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != tok) {
+        if (++spins > HALO_SPIN_LIMIT) {
+            if (lane == 0) __hip_atomic_store(hc->fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(GQ_FLOW_HALO_SLEEP);
+    }
+    Sums<R> S;
+    S.s0 = hc->s[0][lane]; S.sxi = hc->s[1][lane]; S.sxj = hc->s[2][lane];
+    S.sa = hc->s[3][lane]; S.sm = hc->s[4][lane]; S.sx = hc->s[5][lane];
+    return S;
+}
+template <typename R>
+__device__ __forceinline__ void halo_chain_pass(HaloChain<R> *hc, unsigned tok, int w, int lane, const Sums<R> &S)
+{
+    hc->s[0][lane] = S.s0; hc->s[1][lane] = S.sxi; hc->s[2][lane] = S.sxj;
+    hc->s[3][lane] = S.sa; hc->s[4][lane] = S.sm; hc->s[5][lane] = S.sx;
+    __hip_atomic_store(&hc->flag[w], tok, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // The clamped ascent of one interior node from its assembled gradients
 // (gqmap_gpu_mixture.m:41-45; gqmap_ctf.m:34-35), the updated state into dst
 // and the node's exact contributions to the block sums; returns its dalpha.
@@ -923,12 +974,22 @@ __device__ __forceinline__ void tile_totals_tail(const FinParams &F, int total, 
 // row stride grows (the plain form's layout at grows = TM), and every wave
 // of a group runs its tile's halo job itself (5 jobs per wave).
 template <typename R, typename VT, int ENG, int Q, bool EDGE_FIRST, bool COH = false, bool NT = false,
-          bool LIT = false, bool GRP = false, int ROTF = GQ_NODE_ROT_OTHER>
+          bool LIT = false, bool GRP = false, int ROTF = GQ_NODE_ROT_OTHER, int HALO = 0>
 __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, int it, int parity,
                                           int part_r, TileLdsQ<R, Q> &lds, int l0, int l1, double Tcur,
                                           bool tab_ready, unsigned long long *acc_ring = nullptr,
-                                          int grows = 0, bool grouped = false)
+                                          int grows = 0, bool grouped = false, HaloChain<R> *hc = nullptr,
+                                          unsigned halo_tok = 0
+#if GQ_FLOW_TL
+                                          , unsigned long long *tlw = nullptr
+#endif
+                                          )
 {
+    // HALO (the plain form of GRP, !grouped; GQ_FLOW_HALO in gqmap_tuning.h):
+    // 1 the halo job handed round the four waves (hc, halo_tok: HaloChain),
+    // 2 the halo job on another wave in the edge-first workgroups
+    static_assert(HALO == 0 || (GRP && sizeof(R) == 8), "the halo forms: the fp64 dataflow item (one component per item)");
+    constexpr bool CHAIN = HALO == 1;
     static_assert(!LIT || (ENG == 0 && Q == 1 && sizeof(R) == 8), "literal order: fp64 mixture, Q = 1");
     static_assert(!GRP || (Q == 1 && !LIT), "a tile per wave: one lane per node");
     constexpr bool RS = Q == 0;                       // role split (node / edge waves)
@@ -990,8 +1051,12 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
     int htid = rtid;  // the halo edge a lane computes
     if constexpr (GRP) {
         if (grouped) halo_lane = tile >= 0;
+        else if (HALO == 2 && EDGE_FIRST) halo_lane = wave == GQ_FLOW_HALO_ROT_WAVE;
         htid = lane;
     }
+    // the chain runs in the items whose four waves share one tile
+    const bool chain = CHAIN && !grouped;
+    const int cw = __builtin_amdgcn_readfirstlane(wave);
 
     for (int l = l0; l < l1; ++l) {
         // (COH: the dataflow kernel, whose alpha a finalize on another XCD
@@ -1063,7 +1128,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         // lane_combine<Q>, an xor butterfly inside one node's Q adjacent
         // lanes, and a node's lanes are all halo lanes or none (asserted).
         static_assert(HALO_LANES % QA == 0, "a node's lanes share their job count");
-        const int njobs = halo_lane ? 5 : 4;
+        const int njobs = halo_lane || chain ? 5 : 4;
         // Q >= 4 (small grids, about one wave per SIMD: latency-bound) loads
         // job e+1's operands before computing job e
         constexpr bool PREFETCH = QA >= GQ_PREFETCH_MIN_Q;
@@ -1078,19 +1143,44 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         // super engine, which it would push past 256 VGPRs: C4 355 -> 407)
         constexpr bool JOBS_UNROLLED = QA >= GQ_UNROLL_MIN_Q && ENG != 1;
         constexpr int JOB_UNROLL = JOBS_UNROLLED ? 5 : 1;
+        static_assert(!CHAIN || (!PREFETCH && !JOBS_UNROLLED), "the chain: one job body, streamed");
 #pragma unroll JOB_UNROLL
-        for (int e = 0; e < (JOBS_UNROLLED ? 5 : njobs); ++e) {
-            if (JOBS_UNROLLED && e >= njobs) continue;
+        for (int st = 0; st < (JOBS_UNROLLED ? 5 : njobs); ++st) {
+            if (JOBS_UNROLLED && st >= njobs) continue;
+            // The chain: step st of wave w is slice w of the halo job when
+            // st == w, and own job st or st - 1 otherwise -- w own jobs, the
+            // slice, the rest.  Wave w's slice so starts a job after wave
+            // w - 1's: a job less a slice of slack for each hand-over.
+            int e = st;
+            bool slice = false, last = true;  // last: the job's epilogue follows its sums
+            if constexpr (CHAIN)
+                if (chain) {
+                    slice = st == cw;
+                    e = slice ? 4 : st - (st > cw);
+                    last = !slice || cw == 3;
+                }
             EdgeJob<R> jb;
             if (PREFETCH) {
                 jb = next;
-                if (e + 1 < njobs) next = job_at(e + 1);
+                if (st + 1 < njobs) next = job_at(st + 1);
             } else {
                 jb = job_at(e);
             }
             const int dir = jb.dir, uv = jb.uv, hr = jb.hr;
             const bool own_edge = e < 4;
             Grad<R> g{};
+            Sums<R> hs;  // the chain: the halo edge's sums so far
+            if constexpr (CHAIN) {
+                if (slice && cw > 0) {
+#if GQ_FLOW_TL
+                    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();
+#endif
+                    hs = halo_chain_take(hc, halo_tok, cw, lane);
+#if GQ_FLOW_TL
+                    if (tlw && lane == 0) tlw[4 * cw + 3] = __builtin_amdgcn_s_memrealtime() - t_;
+#endif
+                }
+            }
             if (jb.need) {
                 if constexpr (LIT) {
                     g = lit_edge_grad(tab, K2, P.epsn, P.lams, P.guard != 0, T, a, jb.u1, jb.u2, jb.o1, jb.o2, jb.p);
@@ -1105,9 +1195,19 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
                         QA == 1 && ((sizeof(R) == 4 && ENG == 0) ||
                                     (sizeof(R) == 8 && (ENG == 2 || (NT && sizeof(VT) == 4))))
                             ? GQ_PAIR_UNROLL_Q1 : 0;
+                    if constexpr (CHAIN) {
+                        // (own jobs too: the whole range from zero, the same
+                        // sums as edge_sums -- one pair loop in the kernel)
+                        const int np = K2 >> 1;
+                        const int ka = slice ? chain_cut(np, cw, GQ_FLOW_HALO_EPI) : 0;
+                        const int kb = slice ? chain_cut(np, cw + 1, GQ_FLOW_HALO_EPI) : np;
+                        edge_sums_range<PU>(tab, ka, kb, K2, last, P.epsn, c, hs);
+                        if (last) g = edge_epi(hs, c, P.lams, P.guard != 0, T, a, jb.o1, jb.o2, jb.p, ENG == 2);
+                    } else {
                     Sums<R> S = edge_sums_dev<PU>(tab, kj, K2, QA, P.epsn, c);
                     if (QA > 1) S = lane_combine<QA>(S);
                     g = edge_epi(S, c, P.lams, P.guard != 0, T, a, jb.o1, jb.o2, jb.p, ENG == 2);
+                    }
                 }
                 // the edge owns its correlation: clamped ascent right here
                 // (gqmap_gpu_mixture.m:46), nothing else reads drou
@@ -1131,16 +1231,28 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
                 }
             } else if constexpr (GRP) {  // a group's wave fills its own 64 entries, hr < its rows on the left
                 const int hb = grouped ? wave * 64 : 0;
+                if (CHAIN && !last) {  // the sums so far to the next wave of the chain
+                    if constexpr (CHAIN) halo_chain_pass(hc, halo_tok, cw, lane, hs);
+                } else
                 if (dir == 0) { in_up[uv][0][hb + hr * grows] = g.du2; in_up[uv][1][hb + hr * grows] = g.do2; }
                 else if (hr < grows) { in_left[uv][0][hb + hr] = g.du2; in_left[uv][1][hb + hr] = g.do2; }
             } else if (rtid % QA == 0) {
                 if (dir == 0) { in_up[uv][0][hr * TM] = g.du2; in_up[uv][1][hr * TM] = g.do2; }
                 else          { in_left[uv][0][hr] = g.du2; in_left[uv][1][hr] = g.do2; }
             }
+#if GQ_FLOW_TL
+            if (tlw && lane == 0 && own_edge) tlw[4 * cw + 1] = __builtin_amdgcn_s_memrealtime();  // (the last one stays)
+#endif
         }
         }
         if (ph == 0) TL_STAMP(1, __builtin_amdgcn_s_memrealtime());
         }
+#if GQ_FLOW_TL
+        if (tlw && lane == 0) {  // the wave's placement and its arrival at the barrier
+            tlw[4 * cw] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
+            tlw[4 * cw + 2] = __builtin_amdgcn_s_memrealtime();
+        }
+#endif
         __syncthreads();
         TL_STAMP(2, __builtin_amdgcn_s_memrealtime());
         fix128 fda = 0;
@@ -1876,13 +1988,15 @@ __device__ void flow_finalize(const FinParams &F, unsigned *fl, unsigned *bar, u
 // GQ_FLOW_TL (diagnostic builds): per item (j, tile) of a launch that starts
 // at iteration 1, four words at (j * items + tile) -- the claim, the end of the dependency wait,
 // the end of the item, and (XCC_ID << 32 | HW_ID) -- read back with
-// gqmap_debug_flow_timeline (scripts/flow_timeline.py).
-#ifndef GQ_FLOW_TL
-#define GQ_FLOW_TL 0
-#endif
+// gqmap_debug_flow_timeline (scripts/flow_timeline.py); and per wave of the
+// item four more at 16 (j * items + tile) + 4 wave (iter_tile) -- the wave's
+// HW_ID, the end of its last own edge job, its arrival at the item's barrier
+// and the time it waited for the halo chain's hand-over
+// (gqmap_debug_flow_waves, scripts/halo_placement.py).
 #if GQ_FLOW_TL
 constexpr int FLOW_TL_WORDS = 1 << 18;
 __device__ unsigned long long g_flow_tl[FLOW_TL_WORDS];
+__device__ unsigned long long g_flow_tlw[4 * FLOW_TL_WORDS];
 #endif
 // Waves per SIMD the allocation must allow at one lane per node.  2 (<= 256
 // VGPRs): the C2 fp64 kernel takes 215 and spills nothing (at 3, as k_iter
@@ -1965,6 +2079,19 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     constexpr int ROTF = ENG == 0 && Q == 1 && !LIT && W == 0 && sizeof(R) == 8 && is_vvh2<VT>::value
                              ? (GQ_NODE_ROT_FLOW_FP64 | NODE_UNROLL(GQ_NODE_UNROLL_FLOW_FP64))
                              : GQ_NODE_ROT_OTHER;
+    // the halo job of the plain items (iter_tile HALO): the same fp64 item,
+    // and the fp64 ctf levels under their own switch
+    constexpr int HALO = !GRP || LIT || W != 0 || sizeof(R) != 8 ? 0
+                         : ENG == 0 && is_vvh2<VT>::value ? GQ_FLOW_HALO
+                         : ENG == 2 ? GQ_FLOW_HALO_CTF : 0;
+    HaloChain<R> *hc = nullptr;
+    if constexpr (HALO == 1) {
+        __shared__ HaloChain<R> sh_halo;
+        hc = &sh_halo;
+        // (tokens start at 1; the claim's barrier below orders this before the first item)
+        if (threadIdx.x < 4) sh_halo.flag[threadIdx.x] = 0;
+        if (threadIdx.x == 0) sh_halo.fail = bar + BAR_FAIL;
+    }
     const int vr = P.M - (P.tiles_m - 1) * tile_rows(Q);
     const bool groups = GRP && GQ_FLOW_ROWS && vr <= 4;
     const int nlast = groups ? (s0 + nb) / P.tiles_m - s0 / P.tiles_m : 0;  // the band's tiles in the last tile row
@@ -2040,12 +2167,21 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
         // GRP: the calling wave's tile -- the item's own, or its member of a group
         const int wtile = GRP ? __builtin_amdgcn_readfirstlane(grouped ? sh_grp[threadIdx.x >> 6] : tile) : tile;
         const int wrows = grouped ? vr : tile_rows(Q);
+#if GQ_FLOW_TL
+        const size_t tlwi = (size_t)j * nitems + (size_t)tile * L + l;
+        unsigned long long *tlw = (tlwi + 1) * 16 <= (size_t)(4 * FLOW_TL_WORDS) && snap->it == 1 ? g_flow_tlw + tlwi * 16 : nullptr;
+#define GQ_TLW_ARG , tlw
+#else
+#define GQ_TLW_ARG
+#endif
+        // (the halo chain's token: this workgroup's claims only grow)
         if (MIX && edge_first)
-            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP, ROTF>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
-                                                                          wrows, grouped);
+            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+                                                                                wrows, grouped, hc, (unsigned)i + 1 GQ_TLW_ARG);
         else
-            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP, ROTF>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
-                                                                           wrows, grouped);
+            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+                                                                                 wrows, grouped, hc, (unsigned)i + 1 GQ_TLW_ARG);
+#undef GQ_TLW_ARG
         // publish: every wave's stores (state, rou, the slot's sums) are done
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -4526,6 +4662,21 @@ int gqmap_debug_flow_timeline(unsigned long long *out, int n)
 #if GQ_FLOW_TL
     n = std::min(n, FLOW_TL_WORDS);
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_flow_tl), sizeof(unsigned long long) * n) != hipSuccess) return -1;
+    return n;
+#else
+    (void)out;
+    (void)n;
+    return -1;
+#endif
+}
+
+// ... and its per-wave words (16 per item: HW_ID, last own edge job done,
+// at the barrier, hand-over wait of each of the four waves).
+int gqmap_debug_flow_waves(unsigned long long *out, int n)
+{
+#if GQ_FLOW_TL
+    n = std::min(n, 4 * FLOW_TL_WORDS);
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_flow_tlw), sizeof(unsigned long long) * n) != hipSuccess) return -1;
     return n;
 #else
     (void)out;

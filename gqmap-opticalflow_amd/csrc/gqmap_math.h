@@ -846,6 +846,43 @@ GQ_HD Sums<R> edge_sums(TP tab, int k0, int K2, int dk, R eps, const EdgeCoef<R>
         });
     return S;
 }
+// The range form of that loop at one lane per edge (k0 = 0, dk = 1): the
+// mirror pairs [ka, kb) added in increasing k to the carried sums S, then the
+// centre point if `centre` (and K is odd).  edge_sums is the range [0, K^2/2)
+// from zero sums with the centre; cut into consecutive ranges, each starting
+// from the sums the one before left and the last one taking the centre, every
+// accumulator sees edge_sums' fma sequence: the same bits.  (The dataflow
+// item's halo chain hands an edge's sums from wave to wave this way.)
+// Where the halo chain cuts the np pairs: slice w = 0..3 is [chain_cut(w),
+// chain_cut(w + 1)).  epi: the work after the last slice's sums (the centre
+// point and the epilogue) counted in pairs, so the last wave's slice is that
+// much shorter than the others' (0: four equal slices).
+GQ_HD int chain_cut(int np, int w, int epi)
+{
+    const int b = ((np + epi) * w) >> 2;
+    return b < np ? b : np;
+}
+template <int PU = 0, typename R, typename TP>
+GQ_HD void edge_sums_range(TP tab, int ka, int kb, int K2, bool centre, R eps, const EdgeCoef<R> &c, Sums<R> &S)
+{
+    auto pair = [&](int k) {
+        const R p = fma(c.A, tab[tab_at(T_XI, k)], c.B * tab[tab_at(T_XJ, k)]);
+        const R dp = c.C + p, dm = c.C - p;
+        S.add_pair(tab, k, GQ_SQRT(fma(dp, dp, eps)), GQ_SQRT(fma(dm, dm, eps)));
+    };
+    if constexpr (PU == 0) {
+        GQ_PAIR_UNROLL
+        for (int k = ka; k < kb; ++k) pair(k);
+    } else {
+        GQ_PAIR_UNROLL_K(PU)
+        for (int k = ka; k < kb; ++k) pair(k);
+    }
+    if (centre && (K2 & 1)) {
+        const int k = K2 >> 1;
+        const R d = fma(c.A, tab[tab_at(T_XI, k)], fma(c.B, tab[tab_at(T_XJ, k)], c.C));
+        S.add(tab, k, GQ_SQRT(fma(d, d, eps)));
+    }
+}
 template <typename R>
 GQ_HD Grad<R> edge_epi(const Sums<R> &S, const EdgeCoef<R> &c, R lams, bool guard, R T, R a, R o1,
                        R o2, R p, bool raw_energy = false)

@@ -87,6 +87,39 @@
 #ifndef GQ_NODE_ROT_OTHER  // every other pipelined loop: per-launch kernels, fp32, Q >= 2, ctf
 #define GQ_NODE_ROT_OTHER 0
 #endif
+// The halo edge job (the 64 edges entering a tile from above and from the
+// left) of the plain 16 x 16 dataflow item, k_iter_flow at one lane per node
+// (iter_tile HALO; the grouped bottom-row items, the literal order, the
+// 3-wave large-frame form and every per-launch kernel keep their code):
+//   0  wave 0 runs it as a fifth job after its four own
+//   1  the chain: each of the four waves runs a quarter of its pair range for
+//      all 64 edges and hands the sums on through LDS, same order of the sums
+//   2  rotation: as 0, on wave GQ_FLOW_HALO_ROT_WAVE in the edge-first
+//      workgroup of a CU's two (wave 0 in the node-first one)
+// GQ_FLOW_HALO: the fp64 mixture item on the binary16 pair store (C2's
+// kernel) -- 1: C2 fp64 -1.6 / -1.7% in two sessions, every round ahead; 2:
+// +0.2% (the co-resident workgroups' halo waves already sit on different
+// SIMDs); profiles/halo_chain_ab.txt, halo_chain_placement.txt, DESIGN.md 4.
+// GQ_FLOW_HALO_CTF: the fp64 coarse-to-fine levels at one lane per node -- 1:
+// C3 -1.0 / -1.1% (same file; 2 not measured there).
+#ifndef GQ_FLOW_HALO
+#define GQ_FLOW_HALO 1
+#endif
+#ifndef GQ_FLOW_HALO_CTF
+#define GQ_FLOW_HALO_CTF 1
+#endif
+#ifndef GQ_FLOW_HALO_ROT_WAVE
+#define GQ_FLOW_HALO_ROT_WAVE 2
+#endif
+// the chain: the centre point and the epilogue, which the last wave runs
+// after its slice, counted in mirror pairs -- its slice is that much shorter
+// (chain_cut; 0: four equal slices, -1.3%; 8: -1.8%; 12: -1.6%, same session)
+#ifndef GQ_FLOW_HALO_EPI
+#define GQ_FLOW_HALO_EPI 8
+#endif
+#ifndef GQ_FLOW_HALO_SLEEP  // the chain: s_sleep between two polls of the hand-over flag
+#define GQ_FLOW_HALO_SLEEP 1
+#endif
 #ifndef GQ_UNROLL_MIN_Q
 #define GQ_UNROLL_MIN_Q 2
 #endif
