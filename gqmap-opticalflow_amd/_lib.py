@@ -35,6 +35,7 @@ EXPORTS = (
     "gqmap_comm_unique_id", "gqmap_tile_attach_rccl", "gqmap_tile_group_run", "gqmap_tile_attach_host",
     "gqmap_tile_exchange_sizes", "gqmap_tile_exchange_begin", "gqmap_tile_exchange_end",
     "gqmap_cpu_options_default", "gqmap_cpu_run", "gqmap_cpu_run_device", "gqmap_cpu_release", "gqmap_read_flo", "gqmap_write_flo", "gqmap_aepe",
+    "gqmap_init_state_flow", "gqmap_block_match", "gqmap_block_match_host",
 )
 CTF_MAX_LEVELS = 8
 
@@ -148,6 +149,11 @@ def load():
         "gqmap_read_flo": (C.c_int, [C.c_char_p, P(C.c_int), P(C.c_int), _D]),
         "gqmap_write_flo": (C.c_int, [C.c_char_p, _D, C.c_int, C.c_int]),
         "gqmap_aepe": (C.c_int, [_D, _D, u8, C.c_int, C.c_int, C.c_int, _D]),
+        "gqmap_init_state_flow": (C.c_int, [vp, _D, C.c_uint64]),
+        "gqmap_block_match": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _D, _D, _D,
+                                        C.c_int]),
+        "gqmap_block_match_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _D,
+                                             _D]),
         "gqmap_cpu_run": (C.c_int, [P(GqmapCpuOptions), _D, C.c_int, C.c_int, _D, C.c_uint64, _D, _D, _D, _D,
                                     P(C.c_int), C.c_int]),
         "gqmap_cpu_run_device": (C.c_int, [P(GqmapCpuOptions), vp, C.c_int, C.c_int, vp, C.c_uint64, vp, vp, vp,

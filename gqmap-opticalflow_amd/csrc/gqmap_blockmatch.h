@@ -1,0 +1,109 @@
+// Block-matching initialiser (legacy/optical_flow_temp.m:13-32 with
+// legacy/Gaussian_filter.m): the arithmetic, compiled by the kernel
+// (gqmap_blockmatch.hip) and by the host model (gqmap_host.cpp).  Both include
+// this one header and are built with -ffp-contract=off, so they agree bit for
+// bit, ties included.
+//
+// Specification (fp64, fixed order, no contraction).  Indices are 0-based:
+// displacement (u, v), u = 0..2U (rows), v = 0..2V (columns), pairs A(m, n)
+// with B(m + u - U, n + v - V).
+//   w[i], i = 0..2ft   e_i = exp(-(i-ft)^2 / 2 / sigma / sigma) (host exp),
+//                      s = e_0 + e_1 + ... in that order, w_i = e_i / s.
+//                      Gaussian_filter is the outer product w w' up to rounding.
+//   D(m, n)            |A(m, n) - B(m+u-U, n+v-V)| with B = 0 outside the frame
+//                      (img1_ext), and D = 0 for (m, n) outside the frame
+//                      (conv2 'same').
+//   T(m, n)            ((0 + w_0 D(m-ft, n)) + w_1 D(m-ft+1, n)) + ...   (rows)
+//   cost(m, n)         ((0 + w_0 T(m, n-ft)) + w_1 T(m, n-ft+1)) + ...   (columns)
+//   argmin             displacements visited in ascending u + v (2U+1); a
+//                      displacement replaces the best only when cost < best,
+//                      so the FIRST minimum wins ([~,idx] = min(...)).
+//   flow               (V - v, U - u) = (vmt, umt).
+#pragma once
+#include <math.h>
+
+#define GQ_BM_UMAX 32  /* U, V in [0, 32] */
+#define GQ_BM_FTMAX 4  /* ft in [0, 4]    */
+#define GQ_BM_TAPS (2 * GQ_BM_FTMAX + 1)
+
+#ifdef __HIPCC__
+#define GQ_BM_HD __host__ __device__ __forceinline__
+#else
+#define GQ_BM_HD inline
+#endif
+// the tap loops are unrolled in the kernel (weights in registers); the order is the same
+#ifdef __HIP_DEVICE_COMPILE__
+#define GQ_BM_UNROLL _Pragma("unroll")
+#else
+#define GQ_BM_UNROLL
+#endif
+
+namespace gq {
+
+struct BmFilter {
+    double w[GQ_BM_TAPS];
+};
+
+// Host only: the normalised 1-D Gaussian, handed to the kernel as bits.
+inline BmFilter bm_filter(int ft, double sigma)
+{
+    BmFilter f;
+    double s = 0.0;
+    for (int i = 0; i < GQ_BM_TAPS; ++i) {
+        const double k = (double)(i - ft);
+        f.w[i] = i <= 2 * ft ? exp(-(k * k) / 2 / sigma / sigma) : 0.0;
+        if (i <= 2 * ft) s = s + f.w[i];
+    }
+    for (int i = 0; i <= 2 * ft; ++i) f.w[i] = f.w[i] / s;
+    return f;
+}
+
+// Host only: what is wrong with the arguments (nullptr: nothing).
+inline const char *bm_bad_args(int M, int N, int U, int V, int ft, double sigma)
+{
+    if (M < 1 || N < 1) return "empty image";
+    if (U < 0 || U > GQ_BM_UMAX || V < 0 || V > GQ_BM_UMAX) return "U, V outside [0,32]";
+    if (ft < 0 || ft > GQ_BM_FTMAX) return "ft outside [0,4]";
+    if (!(sigma > 0) || !isfinite(sigma)) return "sigma must be finite and > 0";
+    return nullptr;
+}
+
+// T of one (row, column): a and b point at tap 0 (frame row m_first = m - ft)
+// of the A and the displaced B column, rows contiguous; col_in = the column
+// lies inside the frame.  Both arrays must be readable over all 2ft+1 taps.
+GQ_BM_HD double bm_rows(const double *a, const double *b, int ft, const BmFilter &f, int m_first, int M,
+                        bool col_in)
+{
+    double acc = 0.0;
+GQ_BM_UNROLL
+    for (int i = 0; i < GQ_BM_TAPS; ++i) {
+        if (i > 2 * ft) break;
+        const int m = m_first + i;
+        const double d = col_in && m >= 0 && m < M ? fabs(a[i] - b[i]) : 0.0;
+        acc = acc + f.w[i] * d;
+    }
+    return acc;
+}
+
+// cost of one pixel: t points at T(m, n - ft), consecutive columns `stride` apart.
+GQ_BM_HD double bm_cols(const double *t, int stride, int ft, const BmFilter &f)
+{
+    double acc = 0.0;
+GQ_BM_UNROLL
+    for (int j = 0; j < GQ_BM_TAPS; ++j) {
+        if (j > 2 * ft) break;
+        acc = acc + f.w[j] * t[j * stride];
+    }
+    return acc;
+}
+
+// running first-minimum over the displacement index
+GQ_BM_HD void bm_keep(double c, int idx, double &best, int &best_idx)
+{
+    if (c < best) {
+        best = c;
+        best_idx = idx;
+    }
+}
+
+}  // namespace gq

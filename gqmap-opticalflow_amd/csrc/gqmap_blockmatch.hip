@@ -1,0 +1,223 @@
+// Block-matching initialiser on the device (legacy/optical_flow_temp.m:13-32 +
+// legacy/Gaussian_filter.m): Gaussian-filtered SAD over a (2U+1) x (2V+1)
+// window, argmin displacement per pixel.  The arithmetic is gqmap_blockmatch.h
+// (shared with the host model gqmap_block_match_host); this file is the tiling.
+//
+// One workgroup of 256 lanes owns a 32 x TN output tile (rows x columns, TN =
+// 8, 16 or 32).  It stages the A tile (halo ft) and the B window (halo ft+U
+// rows, ft+V columns) in LDS once, zero outside the frame, then loops over the
+// displacements: row pass of the abs-difference into an LDS tile T (32 x
+// (TN+2ft), double-buffered so one barrier per displacement is enough), column
+// pass out of T, running (min, index) in registers.  The cost volume never
+// exists in device memory.  Lanes run along m (the fastest index): global
+// loads, the final stores and every LDS access are unit-stride over a wave half.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "gqmap_internal.h"
+#include "gqmap_blockmatch.h"
+
+namespace gq {
+
+constexpr int BM_TM = 32;        // tile rows = lanes along m
+constexpr int BM_GROUPS = 8;     // column groups of a 256-lane workgroup
+constexpr int BM_THREADS = BM_TM * BM_GROUPS;
+
+// LDS doubles of one workgroup: A tile, B window, two T tiles
+static size_t bm_lds_doubles(int TN, int U, int V, int ft)
+{
+    const size_t AH = BM_TM + 2 * ft, AW = TN + 2 * ft;
+    return AH * AW + (AH + 2 * U) * (AW + 2 * V) + 2 * (size_t)BM_TM * AW;
+}
+
+template <int NPT>  // output columns per lane: TN = 8 * NPT
+__global__ __launch_bounds__(BM_THREADS) void k_block_match(const double *__restrict__ A,
+                                                            const double *__restrict__ B, int M, int N, int U,
+                                                            int V, int ft, BmFilter f, int tiles_m,
+                                                            double *__restrict__ flow, double *__restrict__ cost)
+{
+    extern __shared__ double bm_lds[];
+    constexpr int TN = BM_GROUPS * NPT;
+    const int AH = BM_TM + 2 * ft, AW = TN + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
+    double *As = bm_lds, *Bs = As + AH * AW, *Ts = Bs + BH * BW;
+    const int tid = threadIdx.x;
+    const int m0 = (int)(blockIdx.x % tiles_m) * BM_TM, n0 = (int)(blockIdx.x / tiles_m) * TN;
+
+    for (int t = tid; t < AH * AW; t += BM_THREADS) {
+        const int gm = m0 - ft + t % AH, gn = n0 - ft + t / AH;
+        As[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? A[gm + (int64_t)M * gn] : 0.0;
+    }
+    for (int t = tid; t < BH * BW; t += BM_THREADS) {
+        const int gm = m0 - ft - U + t % BH, gn = n0 - ft - V + t / BH;
+        Bs[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? B[gm + (int64_t)M * gn] : 0.0;
+    }
+    __syncthreads();
+
+    const int lm = tid % BM_TM, cg = tid / BM_TM;
+    double best[NPT];
+    int bidx[NPT];
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        best[k] = INFINITY;
+        bidx[k] = 0;
+    }
+    const int nu = 2 * U + 1, nd = nu * (2 * V + 1);
+    int u = 0, v = 0;
+    for (int idx = 0; idx < nd; ++idx) {
+        double *T = Ts + (idx & 1) * (BM_TM * AW);
+        for (int c = cg; c < AW; c += BM_GROUPS) {
+            const int gn = n0 - ft + c;
+            T[lm + BM_TM * c] = bm_rows(As + lm + AH * c, Bs + (lm + u) + BH * (c + v), ft, f, m0 + lm - ft, M,
+                                        gn >= 0 && gn < N);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < NPT; ++k)
+            bm_keep(bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f), idx, best[k], bidx[k]);
+        if (++u == nu) {
+            u = 0;
+            ++v;
+        }
+    }
+
+    const int64_t MN = (int64_t)M * N;
+    const int gm = m0 + lm;
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const int gn = n0 + cg + BM_GROUPS * k;
+        if (gm < M && gn < N) {
+            const int64_t o = gm + (int64_t)M * gn;
+            flow[o] = (double)(V - bidx[k] / nu);       // vmt
+            flow[o + MN] = (double)(U - bidx[k] % nu);  // umt
+            if (cost) cost[o] = best[k];
+        }
+    }
+}
+
+// Tile width from the workgroups a CU holds at once.  The displacement loop
+// is a chain of LDS round trips with a barrier each, so what hides its latency
+// is resident waves: per CU min(LDS limit, 8 workgroups = the 32-wave cap, the
+// grid's workgroups per CU).  A wider tile repeats less of the row pass in its
+// column halo, so the widest width that keeps 4 workgroups (4 waves per SIMD)
+// resident wins; when none does, the width with the most, ties to the wider.
+static int bm_choose_cols(int M, int N, int U, int V, int ft, int cus)
+{
+    const double lds_cu = 160.0 * 1024, tiles_m = (M + BM_TM - 1) / BM_TM;
+    int cols = 8;
+    double most = -1;
+    for (int tn = 32; tn >= 8; tn /= 2) {
+        const double by_lds = std::floor(lds_cu / (bm_lds_doubles(tn, U, V, ft) * sizeof(double)));
+        const double by_grid = tiles_m * ((N + tn - 1) / tn) / (cus > 0 ? cus : 1);
+        const double res = std::fmin(std::fmin(by_lds, 8.0), by_grid);
+        if (res >= 4) return tn;
+        if (res > most) {
+            most = res;
+            cols = tn;
+        }
+    }
+    return cols;
+}
+
+// tile columns forced by gqmap_debug_block_match_cols (0: chosen from the grid)
+static int g_bm_cols = 0;
+
+template <int NPT>
+static hipError_t bm_launch(const double *dA, const double *dB, int M, int N, int U, int V, int ft,
+                            const BmFilter &f, double *dflow, double *dcost, hipStream_t s)
+{
+    constexpr int TN = BM_GROUPS * NPT;
+    const size_t bytes = bm_lds_doubles(TN, U, V, ft) * sizeof(double);
+    // above 64 KB (up to 117 KB at U = V = 32, ft = 4, TN = 32) the dynamic LDS limit must be raised
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_block_match<NPT>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+    const int tiles_m = (M + BM_TM - 1) / BM_TM, tiles_n = (N + TN - 1) / TN;
+    k_block_match<NPT><<<dim3((unsigned)((int64_t)tiles_m * tiles_n)), dim3(BM_THREADS), bytes, s>>>(
+        dA, dB, M, N, U, V, ft, f, tiles_m, dflow, dcost);
+    return hipGetLastError();
+}
+
+}  // namespace gq
+
+using namespace gq;
+
+namespace {
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+}  // namespace
+
+extern "C" {
+
+// Not in the public header (tests): force the tile width to 8, 16 or 32
+// columns; 0 restores the choice from the grid.  Never changes a result.
+int gqmap_debug_block_match_cols(int cols)
+{
+    if (cols != 0 && cols != 8 && cols != 16 && cols != 32) return -1;
+    g_bm_cols = cols;
+    return 0;
+}
+
+gqmap_status gqmap_block_match(const double *A, const double *B, int M, int N, int U, int V, int ft,
+                               double sigma, double *flow, double *cost, double *elapsed_ms, int device)
+{
+    clear_error();
+    GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "gqmap_block_match: null argument");
+    const char *bad = bm_bad_args(M, N, U, V, ft, sigma);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match: %s (M=%d N=%d U=%d V=%d ft=%d sigma=%g)", bad, M, N,
+             U, V, ft, sigma);
+    GQ_CHECK((int64_t)((M + BM_TM - 1) / BM_TM) * ((N + 7) / 8) <= 0x7fffffff, GQMAP_ERR_INVALID_ARG,
+             "gqmap_block_match: %dx%d has too many tiles", M, N);
+    GQ_CHECK(gqmap_device_count() > device && device >= 0, GQMAP_ERR_NO_DEVICE, "no HIP device %d", device);
+    DeviceGuard dg(device);
+    const BmFilter f = bm_filter(ft, sigma);
+    int cus = 0;
+    GQ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    int cols = g_bm_cols;
+    if (cols == 0) cols = bm_choose_cols(M, N, U, V, ft, cus);
+
+    const size_t bytes = sizeof(double) * (size_t)M * N;
+    DevBuf dA, dB, dflow, dcost;
+    Events ev;
+    GQ_HIP(hipMalloc(&dA.p, bytes));
+    GQ_HIP(hipMalloc(&dB.p, bytes));
+    GQ_HIP(hipMalloc(&dflow.p, 2 * bytes));
+    if (cost) GQ_HIP(hipMalloc(&dcost.p, bytes));
+    GQ_HIP(hipMemcpy(dA.p, A, bytes, hipMemcpyHostToDevice));
+    GQ_HIP(hipMemcpy(dB.p, B, bytes, hipMemcpyHostToDevice));
+    if (elapsed_ms) {
+        GQ_HIP(hipEventCreate(&ev.a));
+        GQ_HIP(hipEventCreate(&ev.b));
+        GQ_HIP(hipEventRecord(ev.a, 0));
+    }
+    const double *a = (const double *)dA.p, *b = (const double *)dB.p;
+    double *df = (double *)dflow.p, *dc = (double *)dcost.p;
+    GQ_HIP(cols == 32   ? bm_launch<4>(a, b, M, N, U, V, ft, f, df, dc, 0)
+           : cols == 16 ? bm_launch<2>(a, b, M, N, U, V, ft, f, df, dc, 0)
+                        : bm_launch<1>(a, b, M, N, U, V, ft, f, df, dc, 0));
+    if (elapsed_ms) {
+        float ms = 0;
+        GQ_HIP(hipEventRecord(ev.b, 0));
+        GQ_HIP(hipEventSynchronize(ev.b));
+        GQ_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+        *elapsed_ms = ms;
+    }
+    GQ_HIP(hipMemcpy(flow, dflow.p, 2 * bytes, hipMemcpyDeviceToHost));
+    if (cost) GQ_HIP(hipMemcpy(cost, dcost.p, bytes, hipMemcpyDeviceToHost));
+    return GQMAP_OK;
+}
+
+}  // extern "C"

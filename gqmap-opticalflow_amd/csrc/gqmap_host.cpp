@@ -8,6 +8,7 @@
 #include <cstring>
 #include <string>
 
+#include "gqmap_blockmatch.h"
 #include "gqmap_internal.h"
 
 namespace gq {
@@ -276,6 +277,56 @@ gqmap_status gqmap_aepe(const double *tflow, const double *flow, const uint8_t *
         total += col / (M - 2 * crop);
     }
     *out = total / (N - 2 * crop);
+    return GQMAP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Block-matching initialiser, host model (legacy/optical_flow_temp.m:13-32):
+// the arithmetic of gqmap_blockmatch.h over zero-padded copies of the frames,
+// one displacement at a time.  Bit for bit what gqmap_block_match computes.
+// ---------------------------------------------------------------------------
+extern "C" {
+
+gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int N, int U, int V, int ft,
+                                    double sigma, double *flow, double *cost)
+{
+    gq::clear_error();
+    GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_host: null argument");
+    const char *bad = gq::bm_bad_args(M, N, U, V, ft, sigma);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_host: %s (M=%d N=%d U=%d V=%d ft=%d sigma=%g)", bad,
+             M, N, U, V, ft, sigma);
+    const gq::BmFilter f = gq::bm_filter(ft, sigma);
+    // Ap(r, c) = A(r - ft, c - ft), Bp(r, c) = B(r - ft - U, c - ft - V), zero outside
+    const size_t AH = (size_t)M + 2 * ft, AW = (size_t)N + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
+    std::vector<double> Ap(AH * AW, 0.0), Bp(BH * BW, 0.0), T((size_t)M * AW), best((size_t)M * N, INFINITY);
+    std::vector<int> bidx((size_t)M * N, 0);
+    for (int n = 0; n < N; ++n) {
+        std::memcpy(&Ap[ft + AH * (n + ft)], A + (size_t)M * n, sizeof(double) * M);
+        std::memcpy(&Bp[ft + U + BH * (n + ft + V)], B + (size_t)M * n, sizeof(double) * M);
+    }
+    const int nu = 2 * U + 1;
+    for (int v = 0; v <= 2 * V; ++v)
+        for (int u = 0; u <= 2 * U; ++u) {
+            for (size_t c = 0; c < AW; ++c) {
+                const bool col_in = c >= (size_t)ft && c < (size_t)ft + N;
+                for (int m = 0; m < M; ++m)
+                    T[m + (size_t)M * c] =
+                        gq::bm_rows(&Ap[m + AH * c], &Bp[m + u + BH * (c + v)], ft, f, m - ft, M, col_in);
+            }
+            for (int n = 0; n < N; ++n)
+                for (int m = 0; m < M; ++m) {
+                    const size_t o = m + (size_t)M * n;
+                    gq::bm_keep(gq::bm_cols(&T[o], M, ft, f), u + v * nu, best[o], bidx[o]);
+                }
+        }
+    const size_t MN = (size_t)M * N;
+    for (size_t o = 0; o < MN; ++o) {
+        flow[o] = (double)(V - bidx[o] / nu);       // vmt
+        flow[o + MN] = (double)(U - bidx[o] % nu);  // umt
+        if (cost) cost[o] = best[o];
+    }
     return GQMAP_OK;
 }
 

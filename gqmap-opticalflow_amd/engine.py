@@ -97,9 +97,12 @@ def rand_uniform(seed: int, stream: int, n: int, first: int = 0) -> np.ndarray:
 
 
 def initial_state(options: dict, M: int, N: int, seed: int = 0, T: float | None = None,
-                  engine: str = "mixture") -> State:
+                  engine: str = "mixture", flow=None) -> State:
     """Host copy of gqmap_init_state: gqmap_gpu_mixture.m:18-24 with the
-    library RNG (what the device generates for the same seed)."""
+    library RNG (what the device generates for the same seed).  With a flow
+    (M x N x 2 on the node grid) the host copy of gqmap_init_state_flow:
+    component 0 of the mean is the flow clamped to the range; NaN and
+    |x| > 1e9 entries keep the draw."""
     L = int(options["L"])
     MNL = M * N * L
     sh = lambda a: a.reshape((M, N, L), order="F")
@@ -116,6 +119,15 @@ def initial_state(options: dict, M: int, N: int, seed: int = 0, T: float | None 
         pn=np.zeros((M, N, L), order="F"), rou=np.zeros((M, N, L, 2, 2), order="F"),
         w=w, alpha=np.exp(w) / np.exp(w).sum(), it=1,
         T=float(options.get("temperature", 0.0) if T is None else T))
+    if flow is not None:
+        flow = np.asarray(flow, dtype=np.float64)
+        if flow.shape != (M, N, 2):
+            raise ValueError(f"flow must be {M}x{N}x2, got {flow.shape}")
+        for plane, x, lo, hi in ((st.muu, flow[:, :, 0], options["minu"], options["maxu"]),
+                                 (st.muv, flow[:, :, 1], options["minv"], options["maxv"])):
+            with np.errstate(invalid="ignore"):
+                known = ~(np.isnan(x) | (np.abs(x) > 1e9))
+                plane[:, :, 0] = np.where(known, np.minimum(np.maximum(x, lo), hi), plane[:, :, 0])
     return st
 
 
@@ -184,6 +196,14 @@ class Engine:
     # -- state -----------------------------------------------------------
     def init_state(self, seed: int = 0) -> None:
         check(self.lib.gqmap_init_state(self.ctx, C.c_uint64(seed)), "gqmap_init_state")
+
+    def init_state_from_flow(self, flow, seed: int = 0) -> None:
+        """gqmap_init_state_flow: init_state(seed) with component 0 of the mean
+        set to `flow` (full node grid M x N x 2) clamped to the options' range."""
+        flow = f64(flow)
+        if flow.shape != (self.M, self.N, 2):
+            raise ValueError(f"flow shape {flow.shape} != node grid {(self.M, self.N, 2)}")
+        check(self.lib.gqmap_init_state_flow(self.ctx, dptr(flow), C.c_uint64(seed)), "gqmap_init_state_flow")
 
     def set_state(self, st: State) -> None:
         for k in ("muu", "muv", "sigu", "sigv", "pn", "rou", "w", "alpha"):
@@ -333,7 +353,7 @@ def aepe(tflow: np.ndarray, flow: np.ndarray, unknown: np.ndarray, crop: int = 1
 
 def _solve(engine: str, options: dict, I1, I2, *, seed: int = 0, precision: str = "fp64",
            device: int = 0, state: State | None = None, verbose: bool = False,
-           eval_every: int = 300):
+           eval_every: int = 300, init_flow=None):
     its = int(options["its"])
     L = int(options["L"])
     sup = engine == "super"
@@ -346,10 +366,12 @@ def _solve(engine: str, options: dict, I1, I2, *, seed: int = 0, precision: str 
     best = np.inf
     mark = None
     with Engine(options, I1, I2, engine, precision, device) as eng:
-        if state is None:
-            eng.init_state(seed)
-        else:
+        if state is not None:
             eng.set_state(state)
+        elif init_flow is not None:
+            eng.init_state_from_flow(init_flow, seed)
+        else:
+            eng.init_state(seed)
         it = 1
         while it <= its:
             # run up to the next evaluation point (it == 1 or it % eval_every == 0)
@@ -395,3 +417,23 @@ def gqmap_gpu_mixture(options: dict, I1, I2, **kw):
 def gqmap_gpuSuper_mix_entropy(options: dict, I1, I2, **kw):
     """[mu, sigma, alpha, AEPE, Energy, logP] = gqmap_gpuSuper_mix_entropy(options, I1, I2)."""
     return _solve("super", options, I1, I2, **kw)
+
+
+def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7,
+                     engine: str = "mixture", device: int = 0, host: bool = False):
+    """A start and a range for the engines from two frames alone
+    (legacy/optical_flow_temp.m:13-32; defaults: the reference's at scale 1,
+    U = floor(6*scale)+1).  The engine's data term compares I1(i, j) with I2 at
+    (i + v, j + u) -- a flow on I1's grid -- so this is block_match(A=I1, B=I2)
+    negated.  Returns (flow, ranges): flow on the node grid (engine="super":
+    the mean of each 4 x 4 block), ranges = dict(minu, maxu, minv, maxv) to merge
+    into the options; pass flow as init_flow= / Engine.init_state_from_flow."""
+    from .ops import block_match
+    out, _ = block_match(I1, I2, U, V, ft, sigma, device=device, host=host)
+    flow = np.asfortranarray(0.0 - out)
+    if engine == "super":
+        M, N = flow.shape[:2]
+        if M % 4 or N % 4:
+            raise ValueError("super engine: image size must be divisible by 4")
+        flow = np.asfortranarray(flow.reshape(M // 4, 4, N // 4, 4, 2).mean(axis=(1, 3)))
+    return flow, dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))

@@ -6,6 +6,7 @@ projsplx        projsplx.m:15-30, batched over columns (projsplx.m:34-67)
 gauss_hermite   GaussHermite_2.m (host)
 imresize        imresize(A, scale) bicubic + antialias (legacy/optical_flow_ctf.m:26-29)
 warp_image      interp2 linear + fillmissing nearest (legacy/optical_flow_ctf.m:30-32)
+block_match     Gaussian-filtered SAD block matching (legacy/optical_flow_temp.m:13-32)
 """
 from __future__ import annotations
 
@@ -92,3 +93,29 @@ def warp_image(V, warp, fill: bool = True, device: int = 0) -> np.ndarray:
     check(_lib.load().gqmap_warp_image(dptr(V), M, N, dptr(warp), int(fill), dptr(out), device),
           "gqmap_warp_image")
     return out
+
+
+def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, device: int = 0,
+                host: bool = False, timed: bool = False):
+    """legacy/optical_flow_temp.m:13-32: per pixel the displacement of the
+    (2U+1) x (2V+1) window with the smallest Gaussian-filtered |A - B shifted|
+    (first minimum).  Returns (flow M x N x 2 = cat(3, vmt, umt), cost M x N):
+    A(m, n) matches B(m - umt, n - vmt).  The reference call is A = img_2,
+    B = img_1.  host=True runs the library's host model of the same arithmetic
+    (no device; bit-identical).  timed=True also returns the kernel time in ms."""
+    A, B = f64(A), f64(B)
+    if A.ndim != 2 or A.shape != B.shape:
+        raise ValueError("block_match: A and B must be equal-size 2-D images")
+    M, N = A.shape
+    flow = np.zeros((M, N, 2), order="F")
+    cost = np.zeros((M, N), order="F")
+    lib = _lib.load()
+    if host:
+        check(lib.gqmap_block_match_host(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), dptr(flow),
+                                         dptr(cost)), "gqmap_block_match_host")
+        return (flow, cost, float("nan")) if timed else (flow, cost)
+    ms = C.c_double(0)
+    check(lib.gqmap_block_match(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), dptr(flow),
+                                dptr(cost), C.cast(C.byref(ms), _lib._D) if timed else None, device),
+          "gqmap_block_match")
+    return (flow, cost, ms.value) if timed else (flow, cost)

@@ -149,6 +149,15 @@ gqmap_status gqmap_set_images(gqmap_ctx *ctx, const double *I1, const double *I2
  * counter-based RNG (SplitMix64; gqmap_rand_uniform) in place of MATLAB's
  * rand(...,'gpuArray'), generated on the device. */
 gqmap_status gqmap_init_state(gqmap_ctx *ctx, uint64_t seed);
+/* gqmap_init_state(ctx, seed), except component l = 0 of the mean:
+ * muu(:,:,1) = min(max(flow(:,:,1), minu), maxu), muv(:,:,1) likewise with
+ * minv/maxv (fp32 contexts: rounded to float).  Entries that are NaN or
+ * |x| > 1e9 (the .flo "unknown" mark) keep the random draw.  Components l >= 1,
+ * sigma, pn, rou, w, alpha, it, T: exactly gqmap_init_state.
+ * flow: FULL node grid M x Ng x 2, host memory (a tile context takes its
+ * columns, as gqmap_set_state does; SUPER: the node grid is image size / 4).
+ * gqmap_block_match below yields such a flow without a ground truth. */
+gqmap_status gqmap_init_state_flow(gqmap_ctx *ctx, const double *flow, uint64_t seed);
 gqmap_status gqmap_set_state(gqmap_ctx *ctx, const gqmap_state *st);
 gqmap_status gqmap_get_state(gqmap_ctx *ctx, gqmap_state *st);
 /* Run up to n_iter iterations (one iteration = gqmap_gpu_mixture.m:27-75
@@ -239,6 +248,28 @@ gqmap_status gqmap_mixture_map(const double *alpha, const double *muu, const dou
 gqmap_status gqmap_flow_to_color(const double *flow, int M, int N, double max_flow,
                                  uint8_t *img, double *flo, double *stats, uint8_t *unknown,
                                  int device);
+
+/* Block-matching initialiser: legacy/optical_flow_temp.m:13-32 +
+ * legacy/Gaussian_filter.m.
+ * A, B: M x N doubles (column-major).  The reference call is A = img_2, B = img_1.
+ * cost(m,n,u,v) = conv2(|A - Bext(u:M+u-1, v:N+v-1)|, g, 'same'), u=1..2U+1, v=1..2V+1,
+ * Bext = B zero-padded by U rows / V columns, g = Gaussian_filter(2*ft+1, sigma),
+ * applied in its separable form (rows, then columns; fixed tap order, see
+ * DESIGN.md);
+ * [~,idx] = min over linear index u + (v-1)(2U+1): the FIRST minimum wins;
+ * umt = U+1-fu, vmt = V+1-fv.
+ * flow (M x N x 2) = cat(3, vmt, umt)  (horizontal first, as :52 passes it to flowToColor);
+ * so A(m,n) matches B(m-umt, n-vmt).  cost (M x N, may be NULL) = the minimum.
+ * U, V in [0,32], ft in [0,4], sigma finite and > 0, M, N >= 1.  The cost
+ * volume never exists in device memory: O(M*N) whatever U and V.
+ * elapsed_ms (may be NULL): kernel time by HIP events, copies excluded. */
+gqmap_status gqmap_block_match(const double *A, const double *B, int M, int N, int U, int V,
+                               int ft, double sigma, double *flow, double *cost,
+                               double *elapsed_ms, int device);
+/* the same arithmetic on the host, no device needed (CPU model and fallback):
+ * bit for bit the result of gqmap_block_match */
+gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int N, int U, int V,
+                                    int ft, double sigma, double *flow, double *cost);
 
 /* imresize(A, scale) (MATLAB default 'bicubic', Antialiasing on for scale<1)
  * of an M x N x C array -> ceil(scale*M) x ceil(scale*N) x C, resampled on the

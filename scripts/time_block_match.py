@@ -1,0 +1,55 @@
+"""Kernel time of gqmap_block_match (HIP events, copies excluded) on a
+RubberWhale frame pair: median of --runs timed calls after a warm-up that keeps
+the GPU busy for --settle seconds (at least one call), so the clock has ramped.
+Beside it the achieved fraction of the 78.6 TF fp64 vector peak, from the
+flops of the separable form per pixel and displacement: (2ft+1) x (subtract,
+multiply, add) in the row pass + (2ft+1) x (multiply, add) in the column pass
+(the row pass repeated in a tile's column halo is not counted).
+
+usage: time_block_match.py [--scale S] [--U U] [--V V] [--ft FT] [--sigma SG] [--runs R] [--cols 0|8|16|32]
+  issue cases: (a) --scale 1 --U 7;  (b) --scale 4 --U 25"""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from gqmap_opticalflow_amd import _lib, block_match, imresize, load_pair  # noqa: E402
+
+PEAK_FP64 = 78.6e12
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--scale", type=float, default=1.0)
+ap.add_argument("--U", type=int, default=7)
+ap.add_argument("--V", type=int, default=None)
+ap.add_argument("--ft", type=int, default=3)
+ap.add_argument("--sigma", type=float, default=1.7)
+ap.add_argument("--runs", type=int, default=5)
+ap.add_argument("--settle", type=float, default=0.5)
+ap.add_argument("--cols", type=int, default=0, help="force the tile width (0: the library's choice)")
+a = ap.parse_args()
+V = a.U if a.V is None else a.V
+
+I1, I2, _ = load_pair("rubberwhale")
+if a.scale != 1:
+    I1, I2 = imresize(I1, a.scale), imresize(I2, a.scale)
+M, N = I1.shape
+f = _lib.load().gqmap_debug_block_match_cols
+f.restype, f.argtypes = C.c_int, [C.c_int]
+assert f(a.cols) == 0
+
+t0, warm = time.perf_counter(), []
+while not warm or time.perf_counter() - t0 < a.settle:
+    warm.append(block_match(I1, I2, a.U, V, a.ft, a.sigma, timed=True)[2])
+ms = [block_match(I1, I2, a.U, V, a.ft, a.sigma, timed=True)[2] for _ in range(a.runs)]
+med = statistics.median(ms)
+flops = float(M) * N * (2 * a.U + 1) * (2 * V + 1) * (2 * a.ft + 1) * 5
+print(f"block_match {M}x{N} U={a.U} V={V} ft={a.ft} sigma={a.sigma} cols={a.cols or 'auto'}: "
+      f"warm-up {len(warm)} calls (first {warm[0]:.3f} ms), runs " + " ".join(f"{x:.3f}" for x in ms) +
+      f" ms, median {med:.3f} ms, {flops / 1e9:.2f} GFLOP, {flops / (med * 1e-3) / 1e12:.2f} TF/s = "
+      f"{100 * flops / (med * 1e-3) / PEAK_FP64:.1f}% of the fp64 vector peak", flush=True)
