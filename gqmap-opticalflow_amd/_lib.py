@@ -36,6 +36,7 @@ EXPORTS = (
     "gqmap_tile_exchange_sizes", "gqmap_tile_exchange_begin", "gqmap_tile_exchange_end",
     "gqmap_cpu_options_default", "gqmap_cpu_run", "gqmap_cpu_run_device", "gqmap_cpu_release", "gqmap_read_flo", "gqmap_write_flo", "gqmap_aepe",
     "gqmap_init_state_flow", "gqmap_block_match", "gqmap_block_match_host",
+    "gqmap_structure_texture", "gqmap_structure_texture_host",
 )
 CTF_MAX_LEVELS = 8
 
@@ -154,6 +155,10 @@ def load():
                                         C.c_int]),
         "gqmap_block_match_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _D,
                                              _D]),
+        "gqmap_structure_texture": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _D, _D,
+                                              _D, C.c_int]),
+        "gqmap_structure_texture_host": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
+                                                   _D, _D]),
         "gqmap_cpu_run": (C.c_int, [P(GqmapCpuOptions), _D, C.c_int, C.c_int, _D, C.c_uint64, _D, _D, _D, _D,
                                     P(C.c_int), C.c_int]),
         "gqmap_cpu_run_device": (C.c_int, [P(GqmapCpuOptions), vp, C.c_int, C.c_int, vp, C.c_uint64, vp, vp, vp,

@@ -10,6 +10,7 @@
 
 #include "gqmap_blockmatch.h"
 #include "gqmap_internal.h"
+#include "gqmap_rof.h"
 
 namespace gq {
 
@@ -327,6 +328,77 @@ gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int
         flow[o + MN] = (double)(U - bidx[o] % nu);  // umt
         if (cost) cost[o] = best[o];
     }
+    return GQMAP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Structure-texture preprocessing, host model (optical_flowSuper.m:7-14 with
+// preprocessed = true): the arithmetic of gqmap_rof.h, one plain Jacobi sweep
+// per iteration over ping-pong copies of p.  Bit for bit what
+// gqmap_structure_texture computes.
+// ---------------------------------------------------------------------------
+extern "C" {
+
+gqmap_status gqmap_structure_texture_host(const double *im, int M, int N, int C, double theta, int n_iter,
+                                          double alp, double *texture, double *structure)
+{
+    gq::clear_error();
+    GQ_CHECK(im && texture, GQMAP_ERR_INVALID_ARG, "gqmap_structure_texture_host: null argument");
+    const char *bad = gq::rof_bad_args(M, N, C, theta, n_iter, alp);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_structure_texture_host: %s (M=%d N=%d C=%d theta=%g n_iter=%d alp=%g)",
+             bad, M, N, C, theta, n_iter, alp);
+    const size_t MN = (size_t)M * N, n_all = MN * C;
+    double lo = INFINITY, hi = -INFINITY;
+    bool nonfinite = false;
+    for (size_t i = 0; i < n_all; ++i) {
+        nonfinite = nonfinite || !std::isfinite(im[i]);
+        lo = std::fmin(lo, im[i]);
+        hi = std::fmax(hi, im[i]);
+    }
+    GQ_CHECK(!gq::rof_bad_range(lo, hi, nonfinite), GQMAP_ERR_INVALID_ARG,
+             "gqmap_structure_texture_host: input range [%g, %g] is zero or not finite", lo, hi);
+    const double delta = gq::rof_delta(theta);
+    std::vector<double> x(n_all), u(MN), p1(n_all, 0.0), p2(n_all, 0.0), t(n_all), s(n_all);
+    for (size_t i = 0; i < n_all; ++i) x[i] = gq::rof_scale_in(im[i], lo, hi);
+    // u (or s) of one plane from its p
+    auto sweep_u = [&](const double *xc, const double *a1, const double *a2, double *out) {
+        for (int n = 0; n < N; ++n)
+            for (int m = 0; m < M; ++m) {
+                const size_t o = m + (size_t)M * n;
+                const double d = gq::rof_div(a1[o], n > 0 ? a1[o - M] : 0.0, a2[o], m > 0 ? a2[o - 1] : 0.0);
+                out[o] = gq::rof_u(xc[o], theta, d);
+            }
+    };
+    for (int c = 0; c < C; ++c) {
+        const double *xc = &x[MN * c];
+        double *a1 = &p1[MN * c], *a2 = &p2[MN * c];
+        for (int it = 0; it < n_iter; ++it) {
+            sweep_u(xc, a1, a2, u.data());
+            // p of a pixel is read by u only, and u is complete: update in place
+            for (int n = 0; n < N; ++n)
+                for (int m = 0; m < M; ++m) {
+                    const size_t o = m + (size_t)M * n;
+                    const double ix = n < N - 1 ? u[o + M] - u[o] : 0.0;
+                    const double iy = m < M - 1 ? u[o + 1] - u[o] : 0.0;
+                    gq::rof_step(a1[o], a2[o], ix, iy, delta);
+                }
+        }
+        sweep_u(xc, a1, a2, &s[MN * c]);
+    }
+    double tlo = INFINITY, thi = -INFINITY;
+    nonfinite = false;
+    for (size_t i = 0; i < n_all; ++i) {
+        t[i] = gq::rof_t(x[i], alp, s[i]);
+        nonfinite = nonfinite || !std::isfinite(t[i]);
+        tlo = std::fmin(tlo, t[i]);
+        thi = std::fmax(thi, t[i]);
+    }
+    GQ_CHECK(!gq::rof_bad_range(tlo, thi, nonfinite), GQMAP_ERR_INVALID_ARG,
+             "gqmap_structure_texture_host: texture range [%g, %g] is zero or not finite", tlo, thi);
+    for (size_t i = 0; i < n_all; ++i) texture[i] = gq::rof_scale_out(t[i], tlo, thi);
+    if (structure) std::memcpy(structure, s.data(), sizeof(double) * n_all);
     return GQMAP_OK;
 }
 

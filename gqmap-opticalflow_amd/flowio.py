@@ -96,12 +96,20 @@ def middlebury_names():
                   if d != "preprocessed" and os.path.isdir(os.path.join(DATA_DIR, d)))
 
 
-def load_pair(name: str, root: str = DATA_DIR):
-    """optical_flow.m:8-13 at scale 1: greyscale double frames + GT flow."""
+def load_pair(name: str, root: str = DATA_DIR, preprocessed: bool = False, **kw):
+    """optical_flow.m:8-13 at scale 1: greyscale double frames + GT flow.
+    preprocessed=True (optical_flowSuper.m:7-14): the structure-texture frames
+    of the pair instead, computed by ops.preprocess_pair(I1, I2, **kw) from the
+    greyscale frames (kw: theta, n_iter, alp, device, host)."""
     d = os.path.join(root, name)
     I1 = rgb2gray(imread(os.path.join(d, "frame10.png"))).astype(np.float64)
     I2 = rgb2gray(imread(os.path.join(d, "frame11.png"))).astype(np.float64)
     gt = read_flow_file(os.path.join(d, "flow10.flo"))
+    if preprocessed:
+        from .ops import preprocess_pair
+        I1, I2 = preprocess_pair(I1, I2, **kw)
+    elif kw:
+        raise TypeError(f"load_pair: {sorted(kw)} only apply with preprocessed=True")
     return np.asfortranarray(I1), np.asfortranarray(I2), gt
 
 

@@ -7,6 +7,7 @@ gauss_hermite   GaussHermite_2.m (host)
 imresize        imresize(A, scale) bicubic + antialias (legacy/optical_flow_ctf.m:26-29)
 warp_image      interp2 linear + fillmissing nearest (legacy/optical_flow_ctf.m:30-32)
 block_match     Gaussian-filtered SAD block matching (legacy/optical_flow_temp.m:13-32)
+structure_texture  ROF structure-texture frames (optical_flowSuper.m:7-14, preprocessed=true)
 """
 from __future__ import annotations
 
@@ -119,3 +120,48 @@ def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, d
                                 dptr(cost), C.cast(C.byref(ms), _lib._D) if timed else None, device),
           "gqmap_block_match")
     return (flow, cost, ms.value) if timed else (flow, cost)
+
+
+def structure_texture(im, theta: float = 0.125, n_iter: int = 100, alp: float = 0.95, device: int = 0,
+                      host: bool = False, structure: bool = False, timed: bool = False):
+    """The generator of the reference's preprocessed frames (optical_flowSuper.m:7-14,
+    preprocessed=true): ROF structure-texture decomposition by Chambolle's dual
+    projection.  im is M x N (x C); all planes are rescaled jointly to [-1, 1],
+    the texture t = x - alp*s jointly to [0, 255].  Returns the texture in im's
+    shape; structure=True returns (texture, s) with s in the [-1, 1] domain
+    (unpinned: the reference holds no structure frames).  host=True runs the
+    library's host model of the same arithmetic (no device; bit-identical).
+    timed=True appends the kernel time in ms."""
+    im = f64(im)
+    if im.ndim not in (2, 3):
+        raise ValueError("structure_texture: im must be M x N or M x N x C")
+    M, N = im.shape[:2]
+    Cn = 1 if im.ndim == 2 else im.shape[2]
+    tex = np.zeros(im.shape, order="F")
+    s = np.zeros(im.shape, order="F") if structure else None
+    sp = dptr(s) if structure else None
+    lib = _lib.load()
+    ms = C.c_double(float("nan"))
+    if host:
+        check(lib.gqmap_structure_texture_host(dptr(im), M, N, Cn, float(theta), int(n_iter), float(alp), dptr(tex),
+                                               sp), "gqmap_structure_texture_host")
+    else:
+        check(lib.gqmap_structure_texture(dptr(im), M, N, Cn, float(theta), int(n_iter), float(alp), dptr(tex), sp,
+                                          C.cast(C.byref(ms), _lib._D) if timed else None, device),
+              "gqmap_structure_texture")
+    out = (tex, s) if structure else (tex,)
+    if timed:
+        out += (ms.value,)
+    return out if len(out) > 1 else out[0]
+
+
+def preprocess_pair(I1, I2, **kw):
+    """(T1, T2): the texture frames of structure_texture(cat(3, I1, I2), **kw),
+    what optical_flowSuper.m loads for a pair when preprocessed=true."""
+    I1, I2 = f64(I1), f64(I2)
+    if I1.ndim != 2 or I1.shape != I2.shape:
+        raise ValueError("preprocess_pair: I1 and I2 must be equal-size 2-D images")
+    if kw.get("structure") or kw.get("timed"):
+        raise ValueError("preprocess_pair returns the two texture frames only")
+    tex = structure_texture(np.stack([I1, I2], axis=2), **kw)
+    return np.asfortranarray(tex[:, :, 0]), np.asfortranarray(tex[:, :, 1])

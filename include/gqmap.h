@@ -271,6 +271,28 @@ gqmap_status gqmap_block_match(const double *A, const double *B, int M, int N, i
 gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int N, int U, int V,
                                     int ft, double sigma, double *flow, double *cost);
 
+/* Structure-texture preprocessing: the generator of the frames
+ * optical_flowSuper.m:7-14 loads with preprocessed = true (ROF decomposition by
+ * Chambolle's dual projection; reference values theta = 1/8, n_iter = 100,
+ * alp = 0.95 on im = cat(3, img1, img2)).
+ * im: M x N x C doubles, column-major.  All planes are rescaled jointly to
+ * [-1, 1]; n_iter Jacobi iterations of the dual variable per plane; structure
+ * s = x + theta*div p, t = x - alp*s; texture = t rescaled jointly to [0, 255]
+ * (operation order: DESIGN.md).  texture: M x N x C.  structure (M x N x C, may
+ * be NULL) = s in the [-1, 1] domain; the reference holds no structure frames,
+ * so it is unpinned.  M, N >= 1, 1 <= C <= 8, theta finite and > 0, n_iter in
+ * [0, 10000], alp finite; a zero or non-finite range of im or of t (constant
+ * or NaN/Inf input) is GQMAP_ERR_INVALID_ARG, where the reference form would
+ * give NaN; the outputs are then untouched.
+ * elapsed_ms (may be NULL): kernel time by HIP events, copies excluded. */
+gqmap_status gqmap_structure_texture(const double *im, int M, int N, int C, double theta, int n_iter,
+                                     double alp, double *texture, double *structure,
+                                     double *elapsed_ms, int device);
+/* the same arithmetic on the host, no device needed: bit for bit the result of
+ * gqmap_structure_texture */
+gqmap_status gqmap_structure_texture_host(const double *im, int M, int N, int C, double theta,
+                                          int n_iter, double alp, double *texture, double *structure);
+
 /* imresize(A, scale) (MATLAB default 'bicubic', Antialiasing on for scale<1)
  * of an M x N x C array -> ceil(scale*M) x ceil(scale*N) x C, resampled on the
  * device (legacy/optical_flow_ctf.m:26-27, 29). */
