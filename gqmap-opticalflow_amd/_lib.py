@@ -37,6 +37,7 @@ EXPORTS = (
     "gqmap_cpu_options_default", "gqmap_cpu_run", "gqmap_cpu_run_device", "gqmap_cpu_release", "gqmap_read_flo", "gqmap_write_flo", "gqmap_aepe",
     "gqmap_init_state_flow", "gqmap_block_match", "gqmap_block_match_host",
     "gqmap_structure_texture", "gqmap_structure_texture_host",
+    "gqmap_block_match_multi", "gqmap_block_match_multi_host", "gqmap_init_state_flows",
 )
 CTF_MAX_LEVELS = 8
 
@@ -155,6 +156,11 @@ def load():
                                         C.c_int]),
         "gqmap_block_match_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _D,
                                              _D]),
+        "gqmap_init_state_flows": (C.c_int, [vp, _D, C.c_int, C.c_uint64]),
+        "gqmap_block_match_multi": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                              C.c_int, _D, _D, _D, C.c_int]),
+        "gqmap_block_match_multi_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                   C.c_int, C.c_int, _D, _D]),
         "gqmap_structure_texture": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _D, _D,
                                               _D, C.c_int]),
         "gqmap_structure_texture_host": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,

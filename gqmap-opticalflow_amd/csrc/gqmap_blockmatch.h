@@ -19,12 +19,29 @@
 //                      displacement replaces the best only when cost < best,
 //                      so the FIRST minimum wins ([~,idx] = min(...)).
 //   flow               (V - v, U - u) = (vmt, umt).
+//
+// Several hypotheses per pixel (gqmap_block_match_multi): cost, filter and
+// displacement order as above; on top of them a hypothesis count H in
+// [1, GQ_BM_HMAX] and a separation sep in [1, 2 GQ_BM_UMAX + 1].
+//   rank 0             the argmin above.
+//   rank k >= 1        the same first-minimum scan (ascending u + v (2U+1),
+//                      replaced only on cost < best) over the ALLOWED
+//                      displacements: max(|u - u_j|, |v - v_j|) >= sep for the
+//                      pick (u_j, v_j) of every earlier rank j < k (bm_far).
+//                      sep = 1: the H smallest, distinct; sep = 2 also forbids
+//                      the 8 neighbours of an earlier pick.
+//   missing ranks      no allowed displacement at rank k: that rank and all
+//                      later ones do not exist (their allowed sets are no
+//                      larger); flow = NaN (bm_nan, one bit pattern), cost = +Inf.
+//   flow               M x N x 2 x H, rank slowest, slice h as `flow` above;
+//                      cost M x N x H.
 #pragma once
 #include <math.h>
 
 #define GQ_BM_UMAX 32  /* U, V in [0, 32] */
 #define GQ_BM_FTMAX 4  /* ft in [0, 4]    */
 #define GQ_BM_TAPS (2 * GQ_BM_FTMAX + 1)
+#define GQ_BM_HMAX 4   /* hypotheses per pixel in [1, 4] */
 
 #ifdef __HIPCC__
 #define GQ_BM_HD __host__ __device__ __forceinline__
@@ -68,6 +85,14 @@ inline const char *bm_bad_args(int M, int N, int U, int V, int ft, double sigma)
     return nullptr;
 }
 
+// Host only: what is wrong with the hypothesis arguments (nullptr: nothing).
+inline const char *bm_bad_multi(int H, int sep)
+{
+    if (H < 1 || H > GQ_BM_HMAX) return "H outside [1,4]";
+    if (sep < 1 || sep > 2 * GQ_BM_UMAX + 1) return "sep outside [1,65]";
+    return nullptr;
+}
+
 // T of one (row, column): a and b point at tap 0 (frame row m_first = m - ft)
 // of the A and the displaced B column, rows contiguous; col_in = the column
 // lies inside the frame.  Both arrays must be readable over all 2ft+1 taps.
@@ -105,5 +130,32 @@ GQ_BM_HD void bm_keep(double c, int idx, double &best, int &best_idx)
         best_idx = idx;
     }
 }
+
+// a pick (u, v) in one int: u, v <= 2 GQ_BM_UMAX fit 8 bits each
+GQ_BM_HD int bm_pack(int u, int v) { return u | (v << 8); }
+
+// (u, v) is at least sep away (Chebyshev) from an earlier pick
+GQ_BM_HD bool bm_far(int u, int v, int pick, int sep)
+{
+    int du = u - (pick & 255), dv = v - (pick >> 8);
+    du = du < 0 ? -du : du;
+    dv = dv < 0 ? -dv : dv;
+    return (du > dv ? du : dv) >= sep;
+}
+
+// bm_keep over the allowed displacements only.  best_idx starts at -1 = "no
+// allowed displacement yet"; the first allowed one takes it whatever its cost,
+// as index 0 does at rank 0, so a cost that is never < best (NaN frames)
+// still names the first allowed displacement.
+GQ_BM_HD void bm_keep_allowed(bool allowed, double c, int idx, double &best, int &best_idx)
+{
+    if (allowed) {
+        if (best_idx < 0) best_idx = idx;
+        bm_keep(c, idx, best, best_idx);
+    }
+}
+
+// the flow of a missing rank: the quiet NaN 0x7ff8000000000000 on host and device
+GQ_BM_HD double bm_nan() { return __builtin_nan(""); }
 
 }  // namespace gq

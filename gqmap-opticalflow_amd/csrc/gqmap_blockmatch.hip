@@ -95,6 +95,100 @@ __global__ __launch_bounds__(BM_THREADS) void k_block_match(const double *__rest
     }
 }
 
+// H hypotheses per pixel (gqmap_blockmatch.h, "Several hypotheses"): the tiles
+// are staged once, then the displacement loop of k_block_match runs once per
+// rank over them.  Every lane builds T at every displacement; only its own
+// bm_keep is gated by the distance to its earlier picks, which stay in
+// registers packed (u, v), one per rank and output column (the rank loop is
+// unrolled over the compile-time bound GQ_BM_HMAX, so no index is dynamic).
+// Each rank's flow and cost leave for memory at the end of its pass.
+// T's buffer parity runs on a counter over ALL passes, not on idx: a pass has
+// an odd number of displacements, so idx & 1 would put the last T of a pass
+// and the first of the next into one buffer, with no barrier between a slow
+// wave's column pass and a fast wave's row pass.  With the running counter
+// consecutive displacements alternate throughout and the one barrier per
+// displacement covers the pass boundary like any other step.
+template <int NPT>
+__global__ __launch_bounds__(BM_THREADS) void k_block_match_multi(const double *__restrict__ A,
+                                                                  const double *__restrict__ B, int M, int N, int U,
+                                                                  int V, int ft, BmFilter f, int tiles_m, int H,
+                                                                  int sep, double *__restrict__ flow,
+                                                                  double *__restrict__ cost)
+{
+    extern __shared__ double bm_lds[];
+    constexpr int TN = BM_GROUPS * NPT;
+    const int AH = BM_TM + 2 * ft, AW = TN + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
+    double *As = bm_lds, *Bs = As + AH * AW, *Ts = Bs + BH * BW;
+    const int tid = threadIdx.x;
+    const int m0 = (int)(blockIdx.x % tiles_m) * BM_TM, n0 = (int)(blockIdx.x / tiles_m) * TN;
+
+    for (int t = tid; t < AH * AW; t += BM_THREADS) {
+        const int gm = m0 - ft + t % AH, gn = n0 - ft + t / AH;
+        As[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? A[gm + (int64_t)M * gn] : 0.0;
+    }
+    for (int t = tid; t < BH * BW; t += BM_THREADS) {
+        const int gm = m0 - ft - U + t % BH, gn = n0 - ft - V + t / BH;
+        Bs[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? B[gm + (int64_t)M * gn] : 0.0;
+    }
+    __syncthreads();
+
+    const int lm = tid % BM_TM, cg = tid / BM_TM;
+    const int nu = 2 * U + 1, nd = nu * (2 * V + 1);
+    const int64_t MN = (int64_t)M * N;
+    const int gm = m0 + lm;
+    int pick[NPT][GQ_BM_HMAX - 1];
+    unsigned done = 0;  // displacements of all passes so far: T's buffer parity
+#pragma unroll
+    for (int r = 0; r < GQ_BM_HMAX; ++r) {
+        if (r >= H) break;
+        double best[NPT];
+        int bidx[NPT];
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            best[k] = INFINITY;
+            bidx[k] = -1;
+        }
+        int u = 0, v = 0;
+        for (int idx = 0; idx < nd; ++idx, ++done) {
+            double *T = Ts + (done & 1u) * (BM_TM * AW);
+            for (int c = cg; c < AW; c += BM_GROUPS) {
+                const int gn = n0 - ft + c;
+                T[lm + BM_TM * c] = bm_rows(As + lm + AH * c, Bs + (lm + u) + BH * (c + v), ft, f, m0 + lm - ft, M,
+                                            gn >= 0 && gn < N);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < NPT; ++k) {
+                bool allowed = true;
+#pragma unroll
+                for (int j = 0; j < GQ_BM_HMAX - 1; ++j)
+                    if (j < r) allowed = allowed && bm_far(u, v, pick[k][j], sep);
+                bm_keep_allowed(allowed, bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f), idx, best[k],
+                                bidx[k]);
+            }
+            if (++u == nu) {
+                u = 0;
+                ++v;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const int gn = n0 + cg + BM_GROUPS * k;
+            const bool found = bidx[k] >= 0;
+            if (gm < M && gn < N) {
+                const int64_t o = gm + (int64_t)M * gn;
+                flow[o + 2 * MN * r] = found ? (double)(V - bidx[k] / nu) : bm_nan();       // vmt
+                flow[o + 2 * MN * r + MN] = found ? (double)(U - bidx[k] % nu) : bm_nan();  // umt
+                if (cost) cost[o + MN * r] = best[k];
+            }
+            // a missing rank adds no exclusion: the allowed set stays empty for the later ranks
+            if (r < GQ_BM_HMAX - 1)
+                pick[k][r < GQ_BM_HMAX - 1 ? r : 0] =
+                    found ? bm_pack(bidx[k] % nu, bidx[k] / nu) : pick[k][r > 0 ? r - 1 : 0];
+        }
+    }
+}
+
 // Tile width from the workgroups a CU holds at once.  The displacement loop
 // is a chain of LDS round trips with a barrier each, so what hides its latency
 // is resident waves: per CU min(LDS limit, 8 workgroups = the 32-wave cap, the
@@ -122,19 +216,25 @@ static int bm_choose_cols(int M, int N, int U, int V, int ft, int cus)
 // tile columns forced by gqmap_debug_block_match_cols (0: chosen from the grid)
 static int g_bm_cols = 0;
 
+// H = 0: the single-hypothesis kernel k_block_match (gqmap_block_match); H >= 1: k_block_match_multi
 template <int NPT>
 static hipError_t bm_launch(const double *dA, const double *dB, int M, int N, int U, int V, int ft,
-                            const BmFilter &f, double *dflow, double *dcost, hipStream_t s)
+                            const BmFilter &f, int H, int sep, double *dflow, double *dcost, hipStream_t s)
 {
     constexpr int TN = BM_GROUPS * NPT;
     const size_t bytes = bm_lds_doubles(TN, U, V, ft) * sizeof(double);
     // above 64 KB (up to 117 KB at U = V = 32, ft = 4, TN = 32) the dynamic LDS limit must be raised
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_block_match<NPT>),
+    hipError_t e = hipFuncSetAttribute(H == 0 ? reinterpret_cast<const void *>(&k_block_match<NPT>)
+                                              : reinterpret_cast<const void *>(&k_block_match_multi<NPT>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
     const int tiles_m = (M + BM_TM - 1) / BM_TM, tiles_n = (N + TN - 1) / TN;
-    k_block_match<NPT><<<dim3((unsigned)((int64_t)tiles_m * tiles_n)), dim3(BM_THREADS), bytes, s>>>(
-        dA, dB, M, N, U, V, ft, f, tiles_m, dflow, dcost);
+    const dim3 grid((unsigned)((int64_t)tiles_m * tiles_n)), block(BM_THREADS);
+    if (H == 0)
+        k_block_match<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, dflow, dcost);
+    else
+        k_block_match_multi<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, H, sep, dflow,
+                                                            dcost);
     return hipGetLastError();
 }
 
@@ -158,6 +258,57 @@ struct Events {
         if (b) (void)hipEventDestroy(b);
     }
 };
+
+// gqmap_block_match (H = 0) and gqmap_block_match_multi (H >= 1) behind one body; who names the caller in errors
+static gqmap_status bm_device(const char *who, const double *A, const double *B, int M, int N, int U, int V, int ft,
+                              double sigma, int H, int sep, double *flow, double *cost, double *elapsed_ms,
+                              int device)
+{
+    clear_error();
+    GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "%s: null argument", who);
+    const char *bad = bm_bad_args(M, N, U, V, ft, sigma);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "%s: %s (M=%d N=%d U=%d V=%d ft=%d sigma=%g)", who, bad, M,
+             N, U, V, ft, sigma);
+    GQ_CHECK((int64_t)((M + BM_TM - 1) / BM_TM) * ((N + 7) / 8) <= 0x7fffffff, GQMAP_ERR_INVALID_ARG,
+             "%s: %dx%d has too many tiles", who, M, N);
+    GQ_CHECK(gqmap_device_count() > device && device >= 0, GQMAP_ERR_NO_DEVICE, "no HIP device %d", device);
+    DeviceGuard dg(device);
+    const BmFilter f = bm_filter(ft, sigma);
+    int cus = 0;
+    GQ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    int cols = g_bm_cols;
+    if (cols == 0) cols = bm_choose_cols(M, N, U, V, ft, cus);
+
+    const size_t bytes = sizeof(double) * (size_t)M * N, ranks = H == 0 ? 1 : (size_t)H;
+    DevBuf dA, dB, dflow, dcost;
+    Events ev;
+    GQ_HIP(hipMalloc(&dA.p, bytes));
+    GQ_HIP(hipMalloc(&dB.p, bytes));
+    GQ_HIP(hipMalloc(&dflow.p, 2 * ranks * bytes));
+    if (cost) GQ_HIP(hipMalloc(&dcost.p, ranks * bytes));
+    GQ_HIP(hipMemcpy(dA.p, A, bytes, hipMemcpyHostToDevice));
+    GQ_HIP(hipMemcpy(dB.p, B, bytes, hipMemcpyHostToDevice));
+    if (elapsed_ms) {
+        GQ_HIP(hipEventCreate(&ev.a));
+        GQ_HIP(hipEventCreate(&ev.b));
+        GQ_HIP(hipEventRecord(ev.a, 0));
+    }
+    const double *a = (const double *)dA.p, *b = (const double *)dB.p;
+    double *df = (double *)dflow.p, *dc = (double *)dcost.p;
+    GQ_HIP(cols == 32   ? bm_launch<4>(a, b, M, N, U, V, ft, f, H, sep, df, dc, 0)
+           : cols == 16 ? bm_launch<2>(a, b, M, N, U, V, ft, f, H, sep, df, dc, 0)
+                        : bm_launch<1>(a, b, M, N, U, V, ft, f, H, sep, df, dc, 0));
+    if (elapsed_ms) {
+        float ms = 0;
+        GQ_HIP(hipEventRecord(ev.b, 0));
+        GQ_HIP(hipEventSynchronize(ev.b));
+        GQ_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+        *elapsed_ms = ms;
+    }
+    GQ_HIP(hipMemcpy(flow, dflow.p, 2 * ranks * bytes, hipMemcpyDeviceToHost));
+    if (cost) GQ_HIP(hipMemcpy(cost, dcost.p, ranks * bytes, hipMemcpyDeviceToHost));
+    return GQMAP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -174,50 +325,18 @@ int gqmap_debug_block_match_cols(int cols)
 gqmap_status gqmap_block_match(const double *A, const double *B, int M, int N, int U, int V, int ft,
                                double sigma, double *flow, double *cost, double *elapsed_ms, int device)
 {
-    clear_error();
-    GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "gqmap_block_match: null argument");
-    const char *bad = bm_bad_args(M, N, U, V, ft, sigma);
-    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match: %s (M=%d N=%d U=%d V=%d ft=%d sigma=%g)", bad, M, N,
-             U, V, ft, sigma);
-    GQ_CHECK((int64_t)((M + BM_TM - 1) / BM_TM) * ((N + 7) / 8) <= 0x7fffffff, GQMAP_ERR_INVALID_ARG,
-             "gqmap_block_match: %dx%d has too many tiles", M, N);
-    GQ_CHECK(gqmap_device_count() > device && device >= 0, GQMAP_ERR_NO_DEVICE, "no HIP device %d", device);
-    DeviceGuard dg(device);
-    const BmFilter f = bm_filter(ft, sigma);
-    int cus = 0;
-    GQ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    int cols = g_bm_cols;
-    if (cols == 0) cols = bm_choose_cols(M, N, U, V, ft, cus);
+    return bm_device("gqmap_block_match", A, B, M, N, U, V, ft, sigma, 0, 1, flow, cost, elapsed_ms, device);
+}
 
-    const size_t bytes = sizeof(double) * (size_t)M * N;
-    DevBuf dA, dB, dflow, dcost;
-    Events ev;
-    GQ_HIP(hipMalloc(&dA.p, bytes));
-    GQ_HIP(hipMalloc(&dB.p, bytes));
-    GQ_HIP(hipMalloc(&dflow.p, 2 * bytes));
-    if (cost) GQ_HIP(hipMalloc(&dcost.p, bytes));
-    GQ_HIP(hipMemcpy(dA.p, A, bytes, hipMemcpyHostToDevice));
-    GQ_HIP(hipMemcpy(dB.p, B, bytes, hipMemcpyHostToDevice));
-    if (elapsed_ms) {
-        GQ_HIP(hipEventCreate(&ev.a));
-        GQ_HIP(hipEventCreate(&ev.b));
-        GQ_HIP(hipEventRecord(ev.a, 0));
-    }
-    const double *a = (const double *)dA.p, *b = (const double *)dB.p;
-    double *df = (double *)dflow.p, *dc = (double *)dcost.p;
-    GQ_HIP(cols == 32   ? bm_launch<4>(a, b, M, N, U, V, ft, f, df, dc, 0)
-           : cols == 16 ? bm_launch<2>(a, b, M, N, U, V, ft, f, df, dc, 0)
-                        : bm_launch<1>(a, b, M, N, U, V, ft, f, df, dc, 0));
-    if (elapsed_ms) {
-        float ms = 0;
-        GQ_HIP(hipEventRecord(ev.b, 0));
-        GQ_HIP(hipEventSynchronize(ev.b));
-        GQ_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-        *elapsed_ms = ms;
-    }
-    GQ_HIP(hipMemcpy(flow, dflow.p, 2 * bytes, hipMemcpyDeviceToHost));
-    if (cost) GQ_HIP(hipMemcpy(cost, dcost.p, bytes, hipMemcpyDeviceToHost));
-    return GQMAP_OK;
+gqmap_status gqmap_block_match_multi(const double *A, const double *B, int M, int N, int U, int V, int ft,
+                                     double sigma, int H, int sep, double *flow, double *cost, double *elapsed_ms,
+                                     int device)
+{
+    clear_error();
+    const char *bad = bm_bad_multi(H, sep);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_multi: %s (H=%d sep=%d)", bad, H, sep);
+    return bm_device("gqmap_block_match_multi", A, B, M, N, U, V, ft, sigma, H, sep, flow, cost, elapsed_ms,
+                     device);
 }
 
 }  // extern "C"

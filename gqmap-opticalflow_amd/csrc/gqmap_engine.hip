@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "gqmap_internal.h"
+#include "gqmap_blockmatch.h"  // GQ_BM_HMAX (gqmap_init_state_flows)
 
 #pragma clang fp contract(off)
 
@@ -2449,20 +2450,22 @@ __global__ void k_init_state(R *st0, R *st1, int64_t MNL, uint64_t b1, uint64_t 
     }
 }
 
-// gqmap_init_state_flow: component l = 0 of the mean from a given flow (this
-// context's columns, M x N x 2 doubles), clamped to the range; NaN and the .flo
-// "unknown" mark (|x| > 1e9) keep the draw k_init_state wrote.  Both buffers.
+// gqmap_init_state_flows: components l < H of the mean from given flows (this
+// context's columns, M x N x 2 x H doubles, slice l for component l), clamped to
+// the range; NaN and the .flo "unknown" mark (|x| > 1e9) keep the draw
+// k_init_state wrote.  Both buffers.  gqmap_init_state_flow is H = 1.
 template <typename R>
-__global__ void k_init_flow(R *st0, R *st1, int64_t MNL, int64_t MN, const double *__restrict__ flow,
+__global__ void k_init_flow(R *st0, R *st1, int64_t MNL, int64_t MN, int H, const double *__restrict__ flow,
                             double minu, double maxu, double minv, double maxv)
 {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= 2 * MN) return;
-    const int q = i >= MN;  // plane 0 = muu, 1 = muv
+    if (i >= 2 * MN * H) return;
+    const int64_t l = i / (2 * MN), r = i % (2 * MN);
+    const int q = r >= MN;  // plane 0 = muu, 1 = muv
     const double x = flow[i], lo = q ? minv : minu, hi = q ? maxv : maxu;
     if (x != x || fabs(x) > 1e9) return;
     const R v = R(fmin(fmax(x, lo), hi));
-    const int64_t o = i - q * MN + q * MNL;
+    const int64_t o = r - q * MN + q * MNL + l * MN;
     st0[o] = v;
     st1[o] = v;
 }
@@ -4321,39 +4324,52 @@ gqmap_status gqmap_init_state(gqmap_ctx *c, uint64_t seed)
     return GQMAP_OK;
 }
 
-gqmap_status gqmap_init_state_flow(gqmap_ctx *c, const double *flow, uint64_t seed)
+// gqmap_init_state_flow (H = 1) and gqmap_init_state_flows behind one body; who names the caller in errors
+static gqmap_status init_state_flows(const char *who, gqmap_ctx *c, const double *flows, int H, uint64_t seed)
 {
     clear_error();
-    GQ_CHECK(c && flow, GQMAP_ERR_INVALID_ARG, "gqmap_init_state_flow: null argument");
-    GQ_CHECK(c->have_images, GQMAP_ERR_STATE, "gqmap_init_state_flow before gqmap_set_images");
+    GQ_CHECK(c && flows, GQMAP_ERR_INVALID_ARG, "%s: null argument", who);
+    GQ_CHECK(H >= 1 && H <= GQ_BM_HMAX && H <= c->L, GQMAP_ERR_INVALID_ARG, "%s: H=%d outside [1, min(%d, L=%d)]",
+             who, H, GQ_BM_HMAX, c->L);
+    GQ_CHECK(c->have_images, GQMAP_ERR_STATE, "%s before gqmap_set_images", who);
     gqmap_status s = gqmap_init_state(c, seed);
     if (s != GQMAP_OK) return s;
     DeviceGuard dg(c->device);
     const gqmap_options &o = c->opt;
-    // flow is the FULL node grid (M x Ng x 2); a tile takes its columns
+    // flows is the FULL node grid (M x Ng x 2 x H); a tile takes its columns
     // n_off .. n_off+N-1 (owned + ghosts), as gqmap_set_state does
     const int64_t MNg = (int64_t)c->M * c->Ng, MN = (int64_t)c->M * c->N;
     double *d_flow = nullptr;
-    GQ_HIP(hipMalloc(&d_flow, sizeof(double) * 2 * (size_t)MN));
+    GQ_HIP(hipMalloc(&d_flow, sizeof(double) * 2 * (size_t)MN * H));
     hipError_t e = hipSuccess;
-    for (int q = 0; q < 2 && e == hipSuccess; ++q)
-        e = hipMemcpyAsync(d_flow + q * MN, flow + q * MNg + (int64_t)c->n_off * c->M, sizeof(double) * (size_t)MN,
+    for (int q = 0; q < 2 * H && e == hipSuccess; ++q)
+        e = hipMemcpyAsync(d_flow + q * MN, flows + q * MNg + (int64_t)c->n_off * c->M, sizeof(double) * (size_t)MN,
                            hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         const int threads = 256;
-        const int blocks = (int)((2 * MN + threads - 1) / threads);
+        const int blocks = (int)((2 * MN * H + threads - 1) / threads);
         if (c->fp32)
             k_init_flow<float><<<blocks, threads, 0, c->stream>>>((float *)c->d_st[0], (float *)c->d_st[1], c->MNL, MN,
-                                                                  d_flow, o.minu, o.maxu, o.minv, o.maxv);
+                                                                  H, d_flow, o.minu, o.maxu, o.minv, o.maxv);
         else
             k_init_flow<double><<<blocks, threads, 0, c->stream>>>((double *)c->d_st[0], (double *)c->d_st[1], c->MNL,
-                                                                   MN, d_flow, o.minu, o.maxu, o.minv, o.maxv);
+                                                                   MN, H, d_flow, o.minu, o.maxu, o.minv, o.maxv);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host pages and d_flow are released below
     (void)hipFree(d_flow);
     GQ_HIP(e);
     return GQMAP_OK;
+}
+
+gqmap_status gqmap_init_state_flow(gqmap_ctx *c, const double *flow, uint64_t seed)
+{
+    return init_state_flows("gqmap_init_state_flow", c, flow, 1, seed);
+}
+
+gqmap_status gqmap_init_state_flows(gqmap_ctx *c, const double *flows, int H, uint64_t seed)
+{
+    return init_state_flows("gqmap_init_state_flows", c, flows, H, seed);
 }
 
 gqmap_status gqmap_set_state(gqmap_ctx *c, const gqmap_state *st)

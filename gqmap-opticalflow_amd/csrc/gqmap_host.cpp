@@ -288,47 +288,76 @@ gqmap_status gqmap_aepe(const double *tflow, const double *flow, const uint8_t *
 // the arithmetic of gqmap_blockmatch.h over zero-padded copies of the frames,
 // one displacement at a time.  Bit for bit what gqmap_block_match computes.
 // ---------------------------------------------------------------------------
-extern "C" {
-
-gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int N, int U, int V, int ft,
-                                    double sigma, double *flow, double *cost)
+// H = 0: the single-hypothesis result (flow M x N x 2); H >= 1: H ranks by the
+// greedy rule of gqmap_blockmatch.h, one pass over the displacements per rank,
+// as the kernel does.  who names the caller in errors.
+static gqmap_status bm_host(const char *who, const double *A, const double *B, int M, int N, int U, int V, int ft,
+                            double sigma, int H, int sep, double *flow, double *cost)
 {
     gq::clear_error();
-    GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_host: null argument");
+    GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "%s: null argument", who);
     const char *bad = gq::bm_bad_args(M, N, U, V, ft, sigma);
-    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_host: %s (M=%d N=%d U=%d V=%d ft=%d sigma=%g)", bad,
-             M, N, U, V, ft, sigma);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "%s: %s (M=%d N=%d U=%d V=%d ft=%d sigma=%g)", who, bad, M, N, U, V, ft,
+             sigma);
     const gq::BmFilter f = gq::bm_filter(ft, sigma);
     // Ap(r, c) = A(r - ft, c - ft), Bp(r, c) = B(r - ft - U, c - ft - V), zero outside
     const size_t AH = (size_t)M + 2 * ft, AW = (size_t)N + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
-    std::vector<double> Ap(AH * AW, 0.0), Bp(BH * BW, 0.0), T((size_t)M * AW), best((size_t)M * N, INFINITY);
-    std::vector<int> bidx((size_t)M * N, 0);
+    const size_t MN = (size_t)M * N;
+    const int ranks = H == 0 ? 1 : H;
+    std::vector<double> Ap(AH * AW, 0.0), Bp(BH * BW, 0.0), T((size_t)M * AW), best(MN);
+    std::vector<int> bidx(MN), pick(MN * GQ_BM_HMAX);
     for (int n = 0; n < N; ++n) {
         std::memcpy(&Ap[ft + AH * (n + ft)], A + (size_t)M * n, sizeof(double) * M);
         std::memcpy(&Bp[ft + U + BH * (n + ft + V)], B + (size_t)M * n, sizeof(double) * M);
     }
     const int nu = 2 * U + 1;
-    for (int v = 0; v <= 2 * V; ++v)
-        for (int u = 0; u <= 2 * U; ++u) {
-            for (size_t c = 0; c < AW; ++c) {
-                const bool col_in = c >= (size_t)ft && c < (size_t)ft + N;
-                for (int m = 0; m < M; ++m)
-                    T[m + (size_t)M * c] =
-                        gq::bm_rows(&Ap[m + AH * c], &Bp[m + u + BH * (c + v)], ft, f, m - ft, M, col_in);
-            }
-            for (int n = 0; n < N; ++n)
-                for (int m = 0; m < M; ++m) {
-                    const size_t o = m + (size_t)M * n;
-                    gq::bm_keep(gq::bm_cols(&T[o], M, ft, f), u + v * nu, best[o], bidx[o]);
+    for (int r = 0; r < ranks; ++r) {
+        std::fill(best.begin(), best.end(), INFINITY);
+        std::fill(bidx.begin(), bidx.end(), -1);
+        for (int v = 0; v <= 2 * V; ++v)
+            for (int u = 0; u <= 2 * U; ++u) {
+                for (size_t c = 0; c < AW; ++c) {
+                    const bool col_in = c >= (size_t)ft && c < (size_t)ft + N;
+                    for (int m = 0; m < M; ++m)
+                        T[m + (size_t)M * c] =
+                            gq::bm_rows(&Ap[m + AH * c], &Bp[m + u + BH * (c + v)], ft, f, m - ft, M, col_in);
                 }
+                for (int n = 0; n < N; ++n)
+                    for (int m = 0; m < M; ++m) {
+                        const size_t o = m + (size_t)M * n;
+                        bool allowed = true;
+                        for (int j = 0; j < r; ++j) allowed = allowed && gq::bm_far(u, v, pick[o + MN * j], sep);
+                        gq::bm_keep_allowed(allowed, gq::bm_cols(&T[o], M, ft, f), u + v * nu, best[o], bidx[o]);
+                    }
+            }
+        double *fl = flow + 2 * MN * r;
+        for (size_t o = 0; o < MN; ++o) {
+            const bool found = bidx[o] >= 0;
+            fl[o] = found ? (double)(V - bidx[o] / nu) : gq::bm_nan();       // vmt
+            fl[o + MN] = found ? (double)(U - bidx[o] % nu) : gq::bm_nan();  // umt
+            if (cost) cost[o + MN * r] = best[o];
+            // a missing rank adds no exclusion: the allowed set stays empty for the later ranks
+            pick[o + MN * r] = found ? gq::bm_pack(bidx[o] % nu, bidx[o] / nu) : pick[o + MN * (r > 0 ? r - 1 : 0)];
         }
-    const size_t MN = (size_t)M * N;
-    for (size_t o = 0; o < MN; ++o) {
-        flow[o] = (double)(V - bidx[o] / nu);       // vmt
-        flow[o + MN] = (double)(U - bidx[o] % nu);  // umt
-        if (cost) cost[o] = best[o];
     }
     return GQMAP_OK;
+}
+
+extern "C" {
+
+gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int N, int U, int V, int ft,
+                                    double sigma, double *flow, double *cost)
+{
+    return bm_host("gqmap_block_match_host", A, B, M, N, U, V, ft, sigma, 0, 1, flow, cost);
+}
+
+gqmap_status gqmap_block_match_multi_host(const double *A, const double *B, int M, int N, int U, int V, int ft,
+                                          double sigma, int H, int sep, double *flow, double *cost)
+{
+    gq::clear_error();
+    const char *bad = gq::bm_bad_multi(H, sep);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_multi_host: %s (H=%d sep=%d)", bad, H, sep);
+    return bm_host("gqmap_block_match_multi_host", A, B, M, N, U, V, ft, sigma, H, sep, flow, cost);
 }
 
 }  // extern "C"

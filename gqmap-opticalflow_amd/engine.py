@@ -102,7 +102,8 @@ def initial_state(options: dict, M: int, N: int, seed: int = 0, T: float | None 
     library RNG (what the device generates for the same seed).  With a flow
     (M x N x 2 on the node grid) the host copy of gqmap_init_state_flow:
     component 0 of the mean is the flow clamped to the range; NaN and
-    |x| > 1e9 entries keep the draw."""
+    |x| > 1e9 entries keep the draw.  With M x N x 2 x H the host copy of
+    gqmap_init_state_flows: component l < H takes slice l in the same way."""
     L = int(options["L"])
     MNL = M * N * L
     sh = lambda a: a.reshape((M, N, L), order="F")
@@ -121,13 +122,16 @@ def initial_state(options: dict, M: int, N: int, seed: int = 0, T: float | None 
         T=float(options.get("temperature", 0.0) if T is None else T))
     if flow is not None:
         flow = np.asarray(flow, dtype=np.float64)
-        if flow.shape != (M, N, 2):
-            raise ValueError(f"flow must be {M}x{N}x2, got {flow.shape}")
-        for plane, x, lo, hi in ((st.muu, flow[:, :, 0], options["minu"], options["maxu"]),
-                                 (st.muv, flow[:, :, 1], options["minv"], options["maxv"])):
-            with np.errstate(invalid="ignore"):
-                known = ~(np.isnan(x) | (np.abs(x) > 1e9))
-                plane[:, :, 0] = np.where(known, np.minimum(np.maximum(x, lo), hi), plane[:, :, 0])
+        if flow.ndim == 3:
+            flow = flow[:, :, :, None]
+        if flow.shape[:3] != (M, N, 2) or flow.ndim != 4 or not 1 <= flow.shape[3] <= L:
+            raise ValueError(f"flow must be {M}x{N}x2 or {M}x{N}x2xH with H <= L, got {flow.shape}")
+        for l in range(flow.shape[3]):
+            for plane, x, lo, hi in ((st.muu, flow[:, :, 0, l], options["minu"], options["maxu"]),
+                                     (st.muv, flow[:, :, 1, l], options["minv"], options["maxv"])):
+                with np.errstate(invalid="ignore"):
+                    known = ~(np.isnan(x) | (np.abs(x) > 1e9))
+                    plane[:, :, l] = np.where(known, np.minimum(np.maximum(x, lo), hi), plane[:, :, l])
     return st
 
 
@@ -199,10 +203,16 @@ class Engine:
 
     def init_state_from_flow(self, flow, seed: int = 0) -> None:
         """gqmap_init_state_flow: init_state(seed) with component 0 of the mean
-        set to `flow` (full node grid M x N x 2) clamped to the options' range."""
+        set to `flow` (full node grid M x N x 2) clamped to the options' range.
+        A flow M x N x 2 x H (H <= L, e.g. from block_match_init(hypotheses=H))
+        seeds components 0..H-1 from its slices (gqmap_init_state_flows)."""
         flow = f64(flow)
+        if flow.ndim == 4 and flow.shape[:3] == (self.M, self.N, 2):
+            check(self.lib.gqmap_init_state_flows(self.ctx, dptr(flow), int(flow.shape[3]), C.c_uint64(seed)),
+                  "gqmap_init_state_flows")
+            return
         if flow.shape != (self.M, self.N, 2):
-            raise ValueError(f"flow shape {flow.shape} != node grid {(self.M, self.N, 2)}")
+            raise ValueError(f"flow shape {flow.shape} != node grid {(self.M, self.N, 2)} (x H)")
         check(self.lib.gqmap_init_state_flow(self.ctx, dptr(flow), C.c_uint64(seed)), "gqmap_init_state_flow")
 
     def set_state(self, st: State) -> None:
@@ -420,20 +430,56 @@ def gqmap_gpuSuper_mix_entropy(options: dict, I1, I2, **kw):
 
 
 def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7,
-                     engine: str = "mixture", device: int = 0, host: bool = False):
+                     engine: str = "mixture", device: int = 0, host: bool = False,
+                     hypotheses: int | None = None, sep: int = 2):
     """A start and a range for the engines from two frames alone
     (legacy/optical_flow_temp.m:13-32; defaults: the reference's at scale 1,
     U = floor(6*scale)+1).  The engine's data term compares I1(i, j) with I2 at
     (i + v, j + u) -- a flow on I1's grid -- so this is block_match(A=I1, B=I2)
     negated.  Returns (flow, ranges): flow on the node grid (engine="super":
     the mean of each 4 x 4 block), ranges = dict(minu, maxu, minv, maxv) to merge
-    into the options; pass flow as init_flow= / Engine.init_state_from_flow."""
+    into the options; pass flow as init_flow= / Engine.init_state_from_flow.
+
+    hypotheses=H returns M x N x 2 x H, one flow per mixture component (ranks of
+    block_match(hypotheses=H, sep=sep), negated; a missing rank stays NaN and
+    keeps the random draw).  engine="super": rank 0 is the block mean as above,
+    whatever H.  A node's rank k >= 1 is the rank-k flow of the ONE pixel of its
+    4 x 4 block whose rank-k cost is smallest (ties: the first pixel in
+    column-major order of the block; NaN when no pixel of the block has that
+    rank).  It is not a mean: the rank-k picks of different pixels are
+    unrelated modes, and averaging them would blend them into a displacement
+    that none of the pixels proposed."""
     from .ops import block_match
-    out, _ = block_match(I1, I2, U, V, ft, sigma, device=device, host=host)
+    sup = engine == "super"
+    if sup and (np.shape(I1)[0] % 4 or np.shape(I1)[1] % 4):
+        raise ValueError("super engine: image size must be divisible by 4")
+    ranges = dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))
+    if hypotheses is None:
+        out, _ = block_match(I1, I2, U, V, ft, sigma, device=device, host=host)
+        flow = np.asfortranarray(0.0 - out)
+        if sup:
+            M, N = flow.shape[:2]
+            flow = np.asfortranarray(flow.reshape(M // 4, 4, N // 4, 4, 2).mean(axis=(1, 3)))
+        return flow, ranges
+    out, cost = block_match(I1, I2, U, V, ft, sigma, device=device, host=host, hypotheses=hypotheses, sep=sep)
     flow = np.asfortranarray(0.0 - out)
-    if engine == "super":
-        M, N = flow.shape[:2]
-        if M % 4 or N % 4:
-            raise ValueError("super engine: image size must be divisible by 4")
-        flow = np.asfortranarray(flow.reshape(M // 4, 4, N // 4, 4, 2).mean(axis=(1, 3)))
-    return flow, dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))
+    if sup:
+        flow = _super_hypotheses(flow, cost)
+    return flow, ranges
+
+
+def _super_hypotheses(flow, cost):
+    """Pixel hypotheses (M x N x 2 x H, M x N x H) on the super node grid; the
+    rule is in block_match_init's docstring."""
+    M, N, _, H = flow.shape
+    m4, n4 = M // 4, N // 4
+    out = np.full((m4, n4, 2, H), np.nan, order="F")
+    out[:, :, :, 0] = flow[:, :, :, 0].reshape(m4, 4, n4, 4, 2).mean(axis=(1, 3))
+    # block pixels in column-major order of the block: index i + 4 j
+    fb = flow.reshape(m4, 4, n4, 4, 2, H).transpose(0, 2, 3, 1, 4, 5).reshape(m4, n4, 16, 2, H)
+    cb = cost.reshape(m4, 4, n4, 4, H).transpose(0, 2, 3, 1, 4).reshape(m4, n4, 16, H)
+    for k in range(1, H):
+        first = np.argmin(cb[:, :, :, k], axis=2)  # +Inf (missing) never beats a finite cost; first on ties
+        pick = np.take_along_axis(fb[:, :, :, :, k], first[:, :, None, None], axis=2)[:, :, 0, :]
+        out[:, :, :, k] = pick  # NaN already when the whole block misses the rank
+    return out

@@ -97,20 +97,40 @@ def warp_image(V, warp, fill: bool = True, device: int = 0) -> np.ndarray:
 
 
 def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, device: int = 0,
-                host: bool = False, timed: bool = False):
+                host: bool = False, timed: bool = False, hypotheses: int | None = None, sep: int = 2):
     """legacy/optical_flow_temp.m:13-32: per pixel the displacement of the
     (2U+1) x (2V+1) window with the smallest Gaussian-filtered |A - B shifted|
     (first minimum).  Returns (flow M x N x 2 = cat(3, vmt, umt), cost M x N):
     A(m, n) matches B(m - umt, n - vmt).  The reference call is A = img_2,
     B = img_1.  host=True runs the library's host model of the same arithmetic
-    (no device; bit-identical).  timed=True also returns the kernel time in ms."""
+    (no device; bit-identical).  timed=True also returns the kernel time in ms.
+
+    hypotheses=H (1..4) returns the H best mutually separated displacements
+    (gqmap_block_match_multi): flow M x N x 2 x H, cost M x N x H.  Rank 0 is
+    the result above; rank k is the first minimum over the displacements at
+    least `sep` away (larger of the row and column distance) from every earlier
+    pick.  A rank with no displacement left is NaN in flow and +Inf in cost."""
     A, B = f64(A), f64(B)
     if A.ndim != 2 or A.shape != B.shape:
         raise ValueError("block_match: A and B must be equal-size 2-D images")
     M, N = A.shape
+    lib = _lib.load()
+    if hypotheses is not None:
+        H = int(hypotheses)
+        if not 1 <= H <= 4:  # the shapes below depend on it; the library checks the rest
+            raise ValueError(f"block_match: hypotheses must be in 1..4, got {hypotheses}")
+        flow = np.zeros((M, N, 2, H), order="F")
+        cost = np.zeros((M, N, H), order="F")
+        args = (dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), H, int(sep), dptr(flow), dptr(cost))
+        if host:
+            check(lib.gqmap_block_match_multi_host(*args), "gqmap_block_match_multi_host")
+            return (flow, cost, float("nan")) if timed else (flow, cost)
+        ms = C.c_double(0)
+        check(lib.gqmap_block_match_multi(*args, C.cast(C.byref(ms), _lib._D) if timed else None, device),
+              "gqmap_block_match_multi")
+        return (flow, cost, ms.value) if timed else (flow, cost)
     flow = np.zeros((M, N, 2), order="F")
     cost = np.zeros((M, N), order="F")
-    lib = _lib.load()
     if host:
         check(lib.gqmap_block_match_host(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), dptr(flow),
                                          dptr(cost)), "gqmap_block_match_host")

@@ -156,8 +156,15 @@ gqmap_status gqmap_init_state(gqmap_ctx *ctx, uint64_t seed);
  * sigma, pn, rou, w, alpha, it, T: exactly gqmap_init_state.
  * flow: FULL node grid M x Ng x 2, host memory (a tile context takes its
  * columns, as gqmap_set_state does; SUPER: the node grid is image size / 4).
- * gqmap_block_match below yields such a flow without a ground truth. */
+ * gqmap_block_match below yields such a flow without a ground truth.
+ * This is gqmap_init_state_flows with H = 1, which seeds several components. */
 gqmap_status gqmap_init_state_flow(gqmap_ctx *ctx, const double *flow, uint64_t seed);
+/* One flow per component: flows is the FULL node grid M x Ng x 2 x H (slice
+ * slowest), 1 <= H <= min(4, L).  Component l < H of muu / muv takes slice l
+ * under the rules of gqmap_init_state_flow (clamped, rounded to float in fp32
+ * contexts, NaN or |x| > 1e9 keep the draw); components l >= H and every other
+ * plane: exactly gqmap_init_state.  gqmap_block_match_multi yields such flows. */
+gqmap_status gqmap_init_state_flows(gqmap_ctx *ctx, const double *flows, int H, uint64_t seed);
 gqmap_status gqmap_set_state(gqmap_ctx *ctx, const gqmap_state *st);
 gqmap_status gqmap_get_state(gqmap_ctx *ctx, gqmap_state *st);
 /* Run up to n_iter iterations (one iteration = gqmap_gpu_mixture.m:27-75
@@ -270,6 +277,23 @@ gqmap_status gqmap_block_match(const double *A, const double *B, int M, int N, i
  * bit for bit the result of gqmap_block_match */
 gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int N, int U, int V,
                                     int ft, double sigma, double *flow, double *cost);
+/* The H best mutually separated displacements per pixel, H in [1,4], sep in
+ * [1,65]: rank 0 is gqmap_block_match's argmin; rank k >= 1 is the first
+ * minimum (same order, same tie rule) over the displacements (u, v) with
+ * max(|u - u_j|, |v - v_j|) >= sep for the pick of every earlier rank j < k.
+ * sep = 1: the H smallest distinct; sep = 2 also forbids an earlier pick's 8
+ * neighbours.  When no displacement is allowed, that rank and all later ones
+ * are missing: flow NaN, cost +Inf.
+ * flow: M x N x 2 x H (rank slowest; slice h laid out and signed as
+ * gqmap_block_match's flow), cost (may be NULL): M x N x H.  One kernel: the
+ * tiles are staged once and scanned H times. */
+gqmap_status gqmap_block_match_multi(const double *A, const double *B, int M, int N, int U, int V,
+                                     int ft, double sigma, int H, int sep, double *flow,
+                                     double *cost, double *elapsed_ms, int device);
+/* the same on the host, bit for bit (NaN patterns included) */
+gqmap_status gqmap_block_match_multi_host(const double *A, const double *B, int M, int N, int U,
+                                          int V, int ft, double sigma, int H, int sep,
+                                          double *flow, double *cost);
 
 /* Structure-texture preprocessing: the generator of the frames
  * optical_flowSuper.m:7-14 loads with preprocessed = true (ROF decomposition by

@@ -6,7 +6,12 @@ flops of the separable form per pixel and displacement: (2ft+1) x (subtract,
 multiply, add) in the row pass + (2ft+1) x (multiply, add) in the column pass
 (the row pass repeated in a tile's column halo is not counted).
 
+--hypotheses H times gqmap_block_match_multi (H ranks, separation --sep)
+instead; its flops are H times the single pass (the exclusion test is integer
+work and not counted).
+
 usage: time_block_match.py [--scale S] [--U U] [--V V] [--ft FT] [--sigma SG] [--runs R] [--cols 0|8|16|32]
+                           [--hypotheses H] [--sep S]
   issue cases: (a) --scale 1 --U 7;  (b) --scale 4 --U 25"""
 import argparse
 import ctypes as C
@@ -32,6 +37,8 @@ ap.add_argument("--sigma", type=float, default=1.7)
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--settle", type=float, default=0.5)
 ap.add_argument("--cols", type=int, default=0, help="force the tile width (0: the library's choice)")
+ap.add_argument("--hypotheses", type=int, default=None, help="H ranks through gqmap_block_match_multi")
+ap.add_argument("--sep", type=int, default=2)
 a = ap.parse_args()
 V = a.U if a.V is None else a.V
 
@@ -43,13 +50,20 @@ f = _lib.load().gqmap_debug_block_match_cols
 f.restype, f.argtypes = C.c_int, [C.c_int]
 assert f(a.cols) == 0
 
+
+
+def call():
+    return block_match(I1, I2, a.U, V, a.ft, a.sigma, timed=True, hypotheses=a.hypotheses, sep=a.sep)[-1]
+
+
 t0, warm = time.perf_counter(), []
 while not warm or time.perf_counter() - t0 < a.settle:
-    warm.append(block_match(I1, I2, a.U, V, a.ft, a.sigma, timed=True)[2])
-ms = [block_match(I1, I2, a.U, V, a.ft, a.sigma, timed=True)[2] for _ in range(a.runs)]
+    warm.append(call())
+ms = [call() for _ in range(a.runs)]
 med = statistics.median(ms)
-flops = float(M) * N * (2 * a.U + 1) * (2 * V + 1) * (2 * a.ft + 1) * 5
-print(f"block_match {M}x{N} U={a.U} V={V} ft={a.ft} sigma={a.sigma} cols={a.cols or 'auto'}: "
+flops = float(M) * N * (2 * a.U + 1) * (2 * V + 1) * (2 * a.ft + 1) * 5 * (a.hypotheses or 1)
+what = "block_match" if a.hypotheses is None else f"block_match_multi H={a.hypotheses} sep={a.sep}"
+print(f"{what} {M}x{N} U={a.U} V={V} ft={a.ft} sigma={a.sigma} cols={a.cols or 'auto'}: "
       f"warm-up {len(warm)} calls (first {warm[0]:.3f} ms), runs " + " ".join(f"{x:.3f}" for x in ms) +
       f" ms, median {med:.3f} ms, {flops / 1e9:.2f} GFLOP, {flops / (med * 1e-3) / 1e12:.2f} TF/s = "
       f"{100 * flops / (med * 1e-3) / PEAK_FP64:.1f}% of the fp64 vector peak", flush=True)
