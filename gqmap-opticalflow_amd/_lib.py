@@ -38,6 +38,7 @@ EXPORTS = (
     "gqmap_init_state_flow", "gqmap_block_match", "gqmap_block_match_host",
     "gqmap_structure_texture", "gqmap_structure_texture_host",
     "gqmap_block_match_multi", "gqmap_block_match_multi_host", "gqmap_init_state_flows",
+    "gqmap_block_match_refine", "gqmap_block_match_refine_host", "gqmap_init_state_seeded",
 )
 CTF_MAX_LEVELS = 8
 
@@ -161,6 +162,11 @@ def load():
                                               C.c_int, _D, _D, _D, C.c_int]),
         "gqmap_block_match_multi_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                                    C.c_int, C.c_int, _D, _D]),
+        "gqmap_block_match_refine": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                               C.c_int, C.c_int, _D, _D, _D, _D, C.c_int]),
+        "gqmap_block_match_refine_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                    C.c_int, C.c_int, _D, _D, _D]),
+        "gqmap_init_state_seeded": (C.c_int, [vp, _D, _D, C.c_int, C.c_uint64]),
         "gqmap_structure_texture": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _D, _D,
                                               _D, C.c_int]),
         "gqmap_structure_texture_host": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,

@@ -35,6 +35,26 @@
 //                      larger); flow = NaN (bm_nan, one bit pattern), cost = +Inf.
 //   flow               M x N x 2 x H, rank slowest, slice h as `flow` above;
 //                      cost M x N x H.
+//
+// Sub-pixel refinement (gqmap_block_match_refine): cost, filter, displacement
+// order, ranks, sep and missing ranks as above; on top of the pick (u0, v0) of
+// rank k with cost c0, a three-point parabola per axis, each axis on its own.
+// The row axis uses (u0 -/+ 1, v0), the column axis (u0, v0 -/+ 1).
+//   cm, cp             the plain filtered costs of the two neighbours on the
+//                      axis, whether or not rank k's separation rule would
+//                      have allowed them.
+//   refinable axis     both neighbours inside the window (1 <= u0 <= 2U - 1,
+//                      1 <= v0 <= 2V - 1), cm >= c0, cp >= c0 and
+//                      den = (cm - c0) + (cp - c0) > 0; a NaN cost fails the
+//                      comparisons (bm_refine).
+//   delta              fmin(fmax((cm - cp) / (den + den), -0.5), 0.5) on a
+//                      refinable axis, 0 otherwise.
+//   flow               ((double)(V - v0) - delta_v, (double)(U - u0) - delta_u),
+//                      layout and sign of `flow` above (plane 0 horizontal).
+//   curv               (den_v, den_u) on refinable axes, 0.0 otherwise; M x N x
+//                      2 x H, laid out as flow.
+//   missing ranks      flow NaN (bm_nan), cost +Inf, curv 0.0.
+//   cost               the cost at the integer pick, as gqmap_block_match_multi.
 #pragma once
 #include <math.h>
 
@@ -157,5 +177,53 @@ GQ_BM_HD void bm_keep_allowed(bool allowed, double c, int idx, double &best, int
 
 // the flow of a missing rank: the quiet NaN 0x7ff8000000000000 on host and device
 GQ_BM_HD double bm_nan() { return __builtin_nan(""); }
+
+// Sub-pixel refinement.  The four neighbour costs of a pick: row axis (u0 -/+ 1,
+// v0), column axis (u0, v0 -/+ 1); NaN until the scan meets the displacement.
+struct BmNear {
+    double um, up, vm, vp;
+};
+
+GQ_BM_HD void bm_near_clear(BmNear &q) { q.um = q.up = q.vm = q.vp = bm_nan(); }
+
+// cost c of displacement (u, v) into q when (u, v) is a neighbour of the packed
+// pick; a missing pick is -1, which unpacks to (255, -1) and has no neighbour.
+GQ_BM_HD void bm_capture(int u, int v, int pick, double c, BmNear &q)
+{
+    const int pu = pick & 255, pv = pick >> 8;
+    if (v == pv) {
+        if (u == pu - 1) q.um = c;
+        if (u == pu + 1) q.up = c;
+    }
+    if (u == pu) {
+        if (v == pv - 1) q.vm = c;
+        if (v == pv + 1) q.vp = c;
+    }
+}
+
+// one axis of the parabola fit: offset delta and curvature den, 0 when the axis
+// is not refinable.  The comparisons are false on NaN.
+GQ_BM_HD void bm_refine(double cm, double c0, double cp, bool in_window, double *delta, double *den)
+{
+    const double d = (cm - c0) + (cp - c0);
+    const bool ok = in_window && cm >= c0 && cp >= c0 && d > 0;
+    *delta = ok ? fmin(fmax((cm - cp) / (d + d), -0.5), 0.5) : 0.0;
+    *den = ok ? d : 0.0;
+}
+
+// flow and curvature of one rank at one pixel from its packed pick (-1: missing)
+// and its neighbour costs: out = {flow_h, flow_v, curv_h, curv_v}, plane 0 horizontal
+GQ_BM_HD void bm_refined(int pick, double c0, const BmNear &q, int U, int V, double out[4])
+{
+    const bool found = pick >= 0;
+    const int pu = pick & 255, pv = pick >> 8;
+    double du, dv, ku, kv;
+    bm_refine(q.um, c0, q.up, found && pu >= 1 && pu <= 2 * U - 1, &du, &ku);
+    bm_refine(q.vm, c0, q.vp, found && pv >= 1 && pv <= 2 * V - 1, &dv, &kv);
+    out[0] = found ? (double)(V - pv) - dv : bm_nan();  // vmt
+    out[1] = found ? (double)(U - pu) - du : bm_nan();  // umt
+    out[2] = kv;
+    out[3] = ku;
+}
 
 }  // namespace gq

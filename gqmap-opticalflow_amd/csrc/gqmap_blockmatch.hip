@@ -189,6 +189,112 @@ __global__ __launch_bounds__(BM_THREADS) void k_block_match_multi(const double *
     }
 }
 
+// H hypotheses with a sub-pixel offset and a curvature each (gqmap_blockmatch.h,
+// "Sub-pixel refinement").  The neighbour costs of a pick are known only once
+// its scan has ended and the cost volume does not exist, so they are computed
+// again: H + 1 scans over the staged tiles.  Scan r < H selects the pick of rank
+// r exactly as k_block_match_multi does; scan r >= 1 also keeps the cost of
+// every displacement that is one step on an axis from rank r - 1's pick
+// (bm_capture: four integer compares per output column and displacement, 4 NPT
+// doubles in registers).  Rank r - 1's flow, cost and curvature leave for
+// memory at the end of scan r; the last scan selects nothing.  T's buffer
+// parity runs on the counter over all scans, for the reason given above.
+template <int NPT>
+__global__ __launch_bounds__(BM_THREADS) void k_block_match_refine(const double *__restrict__ A,
+                                                                   const double *__restrict__ B, int M, int N, int U,
+                                                                   int V, int ft, BmFilter f, int tiles_m, int H,
+                                                                   int sep, double *__restrict__ flow,
+                                                                   double *__restrict__ cost,
+                                                                   double *__restrict__ curv)
+{
+    extern __shared__ double bm_lds[];
+    constexpr int TN = BM_GROUPS * NPT;
+    const int AH = BM_TM + 2 * ft, AW = TN + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
+    double *As = bm_lds, *Bs = As + AH * AW, *Ts = Bs + BH * BW;
+    const int tid = threadIdx.x;
+    const int m0 = (int)(blockIdx.x % tiles_m) * BM_TM, n0 = (int)(blockIdx.x / tiles_m) * TN;
+
+    for (int t = tid; t < AH * AW; t += BM_THREADS) {
+        const int gm = m0 - ft + t % AH, gn = n0 - ft + t / AH;
+        As[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? A[gm + (int64_t)M * gn] : 0.0;
+    }
+    for (int t = tid; t < BH * BW; t += BM_THREADS) {
+        const int gm = m0 - ft - U + t % BH, gn = n0 - ft - V + t / BH;
+        Bs[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? B[gm + (int64_t)M * gn] : 0.0;
+    }
+    __syncthreads();
+
+    const int lm = tid % BM_TM, cg = tid / BM_TM;
+    const int nu = 2 * U + 1, nd = nu * (2 * V + 1);
+    const int64_t MN = (int64_t)M * N;
+    const int gm = m0 + lm;
+    int pick[NPT][GQ_BM_HMAX - 1];
+    int last[NPT];     // rank r - 1's pick, -1 when that rank is missing
+    double c0[NPT];    // its cost
+    BmNear nbr[NPT];  // its neighbour costs, filled during scan r
+    unsigned done = 0;  // displacements of all scans so far: T's buffer parity
+#pragma unroll
+    for (int r = 0; r <= GQ_BM_HMAX; ++r) {
+        if (r > H) break;
+        double best[NPT];
+        int bidx[NPT];
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            best[k] = INFINITY;
+            bidx[k] = -1;
+            bm_near_clear(nbr[k]);
+        }
+        int u = 0, v = 0;
+        for (int idx = 0; idx < nd; ++idx, ++done) {
+            double *T = Ts + (done & 1u) * (BM_TM * AW);
+            for (int c = cg; c < AW; c += BM_GROUPS) {
+                const int gn = n0 - ft + c;
+                T[lm + BM_TM * c] = bm_rows(As + lm + AH * c, Bs + (lm + u) + BH * (c + v), ft, f, m0 + lm - ft, M,
+                                            gn >= 0 && gn < N);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < NPT; ++k) {
+                const double c = bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f);
+                if (r < H) {
+                    bool allowed = true;
+#pragma unroll
+                    for (int j = 0; j < GQ_BM_HMAX - 1; ++j)
+                        if (j < r) allowed = allowed && bm_far(u, v, pick[k][j], sep);
+                    bm_keep_allowed(allowed, c, idx, best[k], bidx[k]);
+                }
+                if (r >= 1) bm_capture(u, v, last[k], c, nbr[k]);
+            }
+            if (++u == nu) {
+                u = 0;
+                ++v;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const int gn = n0 + cg + BM_GROUPS * k;
+            if (r >= 1 && gm < M && gn < N) {
+                const int64_t o = gm + (int64_t)M * gn + 2 * MN * (r - 1);
+                double out[4];
+                bm_refined(last[k], c0[k], nbr[k], U, V, out);
+                flow[o] = out[0];
+                flow[o + MN] = out[1];
+                if (cost) cost[gm + (int64_t)M * gn + MN * (r - 1)] = c0[k];
+                if (curv) {
+                    curv[o] = out[2];
+                    curv[o + MN] = out[3];
+                }
+            }
+            const bool found = bidx[k] >= 0;
+            last[k] = found ? bm_pack(bidx[k] % nu, bidx[k] / nu) : -1;
+            c0[k] = best[k];
+            // a missing rank adds no exclusion: the allowed set stays empty for the later ranks
+            if (r < GQ_BM_HMAX - 1)
+                pick[k][r < GQ_BM_HMAX - 1 ? r : 0] = found ? last[k] : pick[k][r > 0 ? r - 1 : 0];
+        }
+    }
+}
+
 // Tile width from the workgroups a CU holds at once.  The displacement loop
 // is a chain of LDS round trips with a barrier each, so what hides its latency
 // is resident waves: per CU min(LDS limit, 8 workgroups = the 32-wave cap, the
@@ -216,22 +322,28 @@ static int bm_choose_cols(int M, int N, int U, int V, int ft, int cus)
 // tile columns forced by gqmap_debug_block_match_cols (0: chosen from the grid)
 static int g_bm_cols = 0;
 
-// H = 0: the single-hypothesis kernel k_block_match (gqmap_block_match); H >= 1: k_block_match_multi
+// H = 0: the single-hypothesis kernel k_block_match (gqmap_block_match); H >= 1: k_block_match_multi, or
+// with refine k_block_match_refine (dcurv may be null)
 template <int NPT>
 static hipError_t bm_launch(const double *dA, const double *dB, int M, int N, int U, int V, int ft,
-                            const BmFilter &f, int H, int sep, double *dflow, double *dcost, hipStream_t s)
+                            const BmFilter &f, int H, int sep, bool refine, double *dflow, double *dcost,
+                            double *dcurv, hipStream_t s)
 {
     constexpr int TN = BM_GROUPS * NPT;
     const size_t bytes = bm_lds_doubles(TN, U, V, ft) * sizeof(double);
     // above 64 KB (up to 117 KB at U = V = 32, ft = 4, TN = 32) the dynamic LDS limit must be raised
-    hipError_t e = hipFuncSetAttribute(H == 0 ? reinterpret_cast<const void *>(&k_block_match<NPT>)
-                                              : reinterpret_cast<const void *>(&k_block_match_multi<NPT>),
+    hipError_t e = hipFuncSetAttribute(H == 0   ? reinterpret_cast<const void *>(&k_block_match<NPT>)
+                                       : refine ? reinterpret_cast<const void *>(&k_block_match_refine<NPT>)
+                                                : reinterpret_cast<const void *>(&k_block_match_multi<NPT>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
     const int tiles_m = (M + BM_TM - 1) / BM_TM, tiles_n = (N + TN - 1) / TN;
     const dim3 grid((unsigned)((int64_t)tiles_m * tiles_n)), block(BM_THREADS);
     if (H == 0)
         k_block_match<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, dflow, dcost);
+    else if (refine)
+        k_block_match_refine<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, H, sep, dflow,
+                                                             dcost, dcurv);
     else
         k_block_match_multi<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, H, sep, dflow,
                                                             dcost);
@@ -259,10 +371,11 @@ struct Events {
     }
 };
 
-// gqmap_block_match (H = 0) and gqmap_block_match_multi (H >= 1) behind one body; who names the caller in errors
+// gqmap_block_match (H = 0), gqmap_block_match_multi (H >= 1) and gqmap_block_match_refine (H >= 1, refine; curv
+// may be null) behind one body; who names the caller in errors
 static gqmap_status bm_device(const char *who, const double *A, const double *B, int M, int N, int U, int V, int ft,
-                              double sigma, int H, int sep, double *flow, double *cost, double *elapsed_ms,
-                              int device)
+                              double sigma, int H, int sep, bool refine, double *flow, double *cost, double *curv,
+                              double *elapsed_ms, int device)
 {
     clear_error();
     GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "%s: null argument", who);
@@ -280,12 +393,13 @@ static gqmap_status bm_device(const char *who, const double *A, const double *B,
     if (cols == 0) cols = bm_choose_cols(M, N, U, V, ft, cus);
 
     const size_t bytes = sizeof(double) * (size_t)M * N, ranks = H == 0 ? 1 : (size_t)H;
-    DevBuf dA, dB, dflow, dcost;
+    DevBuf dA, dB, dflow, dcost, dcurv;
     Events ev;
     GQ_HIP(hipMalloc(&dA.p, bytes));
     GQ_HIP(hipMalloc(&dB.p, bytes));
     GQ_HIP(hipMalloc(&dflow.p, 2 * ranks * bytes));
     if (cost) GQ_HIP(hipMalloc(&dcost.p, ranks * bytes));
+    if (refine && curv) GQ_HIP(hipMalloc(&dcurv.p, 2 * ranks * bytes));
     GQ_HIP(hipMemcpy(dA.p, A, bytes, hipMemcpyHostToDevice));
     GQ_HIP(hipMemcpy(dB.p, B, bytes, hipMemcpyHostToDevice));
     if (elapsed_ms) {
@@ -294,10 +408,10 @@ static gqmap_status bm_device(const char *who, const double *A, const double *B,
         GQ_HIP(hipEventRecord(ev.a, 0));
     }
     const double *a = (const double *)dA.p, *b = (const double *)dB.p;
-    double *df = (double *)dflow.p, *dc = (double *)dcost.p;
-    GQ_HIP(cols == 32   ? bm_launch<4>(a, b, M, N, U, V, ft, f, H, sep, df, dc, 0)
-           : cols == 16 ? bm_launch<2>(a, b, M, N, U, V, ft, f, H, sep, df, dc, 0)
-                        : bm_launch<1>(a, b, M, N, U, V, ft, f, H, sep, df, dc, 0));
+    double *df = (double *)dflow.p, *dc = (double *)dcost.p, *dk = (double *)dcurv.p;
+    GQ_HIP(cols == 32   ? bm_launch<4>(a, b, M, N, U, V, ft, f, H, sep, refine, df, dc, dk, 0)
+           : cols == 16 ? bm_launch<2>(a, b, M, N, U, V, ft, f, H, sep, refine, df, dc, dk, 0)
+                        : bm_launch<1>(a, b, M, N, U, V, ft, f, H, sep, refine, df, dc, dk, 0));
     if (elapsed_ms) {
         float ms = 0;
         GQ_HIP(hipEventRecord(ev.b, 0));
@@ -307,6 +421,7 @@ static gqmap_status bm_device(const char *who, const double *A, const double *B,
     }
     GQ_HIP(hipMemcpy(flow, dflow.p, 2 * ranks * bytes, hipMemcpyDeviceToHost));
     if (cost) GQ_HIP(hipMemcpy(cost, dcost.p, ranks * bytes, hipMemcpyDeviceToHost));
+    if (dcurv.p) GQ_HIP(hipMemcpy(curv, dcurv.p, 2 * ranks * bytes, hipMemcpyDeviceToHost));
     return GQMAP_OK;
 }
 }  // namespace
@@ -325,7 +440,8 @@ int gqmap_debug_block_match_cols(int cols)
 gqmap_status gqmap_block_match(const double *A, const double *B, int M, int N, int U, int V, int ft,
                                double sigma, double *flow, double *cost, double *elapsed_ms, int device)
 {
-    return bm_device("gqmap_block_match", A, B, M, N, U, V, ft, sigma, 0, 1, flow, cost, elapsed_ms, device);
+    return bm_device("gqmap_block_match", A, B, M, N, U, V, ft, sigma, 0, 1, false, flow, cost, nullptr, elapsed_ms,
+                     device);
 }
 
 gqmap_status gqmap_block_match_multi(const double *A, const double *B, int M, int N, int U, int V, int ft,
@@ -335,8 +451,19 @@ gqmap_status gqmap_block_match_multi(const double *A, const double *B, int M, in
     clear_error();
     const char *bad = bm_bad_multi(H, sep);
     GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_multi: %s (H=%d sep=%d)", bad, H, sep);
-    return bm_device("gqmap_block_match_multi", A, B, M, N, U, V, ft, sigma, H, sep, flow, cost, elapsed_ms,
-                     device);
+    return bm_device("gqmap_block_match_multi", A, B, M, N, U, V, ft, sigma, H, sep, false, flow, cost, nullptr,
+                     elapsed_ms, device);
+}
+
+gqmap_status gqmap_block_match_refine(const double *A, const double *B, int M, int N, int U, int V, int ft,
+                                      double sigma, int H, int sep, double *flow, double *cost, double *curv,
+                                      double *elapsed_ms, int device)
+{
+    clear_error();
+    const char *bad = bm_bad_multi(H, sep);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_refine: %s (H=%d sep=%d)", bad, H, sep);
+    return bm_device("gqmap_block_match_refine", A, B, M, N, U, V, ft, sigma, H, sep, true, flow, cost, curv,
+                     elapsed_ms, device);
 }
 
 }  // extern "C"

@@ -2470,6 +2470,25 @@ __global__ void k_init_flow(R *st0, R *st1, int64_t MNL, int64_t MN, int H, cons
     st1[o] = v;
 }
 
+// gqmap_init_state_seeded: components l < H of sigma from given widths (laid
+// out as k_init_flow's flows: plane 0 = sigu, 1 = sigv), clamped to [sig_lo,
+// sig_hi]; entries that are not finite and > 0 keep the draw k_init_state wrote.
+template <typename R>
+__global__ void k_init_sigma(R *st0, R *st1, int64_t MNL, int64_t MN, int H, const double *__restrict__ sig,
+                             double sig_lo, double sig_hi)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= 2 * MN * H) return;
+    const int64_t l = i / (2 * MN), r = i % (2 * MN);
+    const int q = r >= MN;  // plane 0 = sigu, 1 = sigv
+    const double x = sig[i];
+    if (!(x > 0) || fabs(x) == INFINITY) return;
+    const R v = R(fmin(fmax(x, sig_lo), sig_hi));
+    const int64_t o = r - q * MN + (2 + q) * MNL + l * MN;
+    st0[o] = v;
+    st1[o] = v;
+}
+
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
@@ -4324,8 +4343,10 @@ gqmap_status gqmap_init_state(gqmap_ctx *c, uint64_t seed)
     return GQMAP_OK;
 }
 
-// gqmap_init_state_flow (H = 1) and gqmap_init_state_flows behind one body; who names the caller in errors
-static gqmap_status init_state_flows(const char *who, gqmap_ctx *c, const double *flows, int H, uint64_t seed)
+// gqmap_init_state_flow (H = 1), gqmap_init_state_flows and gqmap_init_state_seeded (sigmas, may be null) behind
+// one body; who names the caller in errors
+static gqmap_status init_state_flows(const char *who, gqmap_ctx *c, const double *flows, const double *sigmas, int H,
+                                     uint64_t seed)
 {
     clear_error();
     GQ_CHECK(c && flows, GQMAP_ERR_INVALID_ARG, "%s: null argument", who);
@@ -4339,12 +4360,17 @@ static gqmap_status init_state_flows(const char *who, gqmap_ctx *c, const double
     // flows is the FULL node grid (M x Ng x 2 x H); a tile takes its columns
     // n_off .. n_off+N-1 (owned + ghosts), as gqmap_set_state does
     const int64_t MNg = (int64_t)c->M * c->Ng, MN = (int64_t)c->M * c->N;
+    // sigmas, when given, behind the flows in the one staging buffer
+    const int64_t per = 2 * MN * H;
     double *d_flow = nullptr;
-    GQ_HIP(hipMalloc(&d_flow, sizeof(double) * 2 * (size_t)MN * H));
+    GQ_HIP(hipMalloc(&d_flow, sizeof(double) * (size_t)per * (sigmas ? 2 : 1)));
     hipError_t e = hipSuccess;
     for (int q = 0; q < 2 * H && e == hipSuccess; ++q)
         e = hipMemcpyAsync(d_flow + q * MN, flows + q * MNg + (int64_t)c->n_off * c->M, sizeof(double) * (size_t)MN,
                            hipMemcpyHostToDevice, c->stream);
+    for (int q = 0; sigmas && q < 2 * H && e == hipSuccess; ++q)
+        e = hipMemcpyAsync(d_flow + per + q * MN, sigmas + q * MNg + (int64_t)c->n_off * c->M,
+                           sizeof(double) * (size_t)MN, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         const int threads = 256;
         const int blocks = (int)((2 * MN * H + threads - 1) / threads);
@@ -4354,6 +4380,12 @@ static gqmap_status init_state_flows(const char *who, gqmap_ctx *c, const double
         else
             k_init_flow<double><<<blocks, threads, 0, c->stream>>>((double *)c->d_st[0], (double *)c->d_st[1], c->MNL,
                                                                    MN, H, d_flow, o.minu, o.maxu, o.minv, o.maxv);
+        if (sigmas && c->fp32)
+            k_init_sigma<float><<<blocks, threads, 0, c->stream>>>((float *)c->d_st[0], (float *)c->d_st[1], c->MNL,
+                                                                   MN, H, d_flow + per, o.sig_lo, o.sig_hi);
+        else if (sigmas)
+            k_init_sigma<double><<<blocks, threads, 0, c->stream>>>((double *)c->d_st[0], (double *)c->d_st[1],
+                                                                    c->MNL, MN, H, d_flow + per, o.sig_lo, o.sig_hi);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host pages and d_flow are released below
@@ -4364,12 +4396,17 @@ static gqmap_status init_state_flows(const char *who, gqmap_ctx *c, const double
 
 gqmap_status gqmap_init_state_flow(gqmap_ctx *c, const double *flow, uint64_t seed)
 {
-    return init_state_flows("gqmap_init_state_flow", c, flow, 1, seed);
+    return init_state_flows("gqmap_init_state_flow", c, flow, nullptr, 1, seed);
 }
 
 gqmap_status gqmap_init_state_flows(gqmap_ctx *c, const double *flows, int H, uint64_t seed)
 {
-    return init_state_flows("gqmap_init_state_flows", c, flows, H, seed);
+    return init_state_flows("gqmap_init_state_flows", c, flows, nullptr, H, seed);
+}
+
+gqmap_status gqmap_init_state_seeded(gqmap_ctx *c, const double *flows, const double *sigmas, int H, uint64_t seed)
+{
+    return init_state_flows("gqmap_init_state_seeded", c, flows, sigmas, H, seed);
 }
 
 gqmap_status gqmap_set_state(gqmap_ctx *c, const gqmap_state *st)

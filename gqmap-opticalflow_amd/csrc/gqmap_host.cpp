@@ -290,9 +290,12 @@ gqmap_status gqmap_aepe(const double *tflow, const double *flow, const uint8_t *
 // ---------------------------------------------------------------------------
 // H = 0: the single-hypothesis result (flow M x N x 2); H >= 1: H ranks by the
 // greedy rule of gqmap_blockmatch.h, one pass over the displacements per rank,
-// as the kernel does.  who names the caller in errors.
+// as the kernel does.  refine (H >= 1): the sub-pixel flow and the curvature
+// (curv may be null) by H + 1 passes, pass r >= 1 also keeping the neighbour
+// costs of rank r - 1's pick, again as the kernel does.  who names the caller
+// in errors.
 static gqmap_status bm_host(const char *who, const double *A, const double *B, int M, int N, int U, int V, int ft,
-                            double sigma, int H, int sep, double *flow, double *cost)
+                            double sigma, int H, int sep, bool refine, double *flow, double *cost, double *curv)
 {
     gq::clear_error();
     GQ_CHECK(A && B && flow, GQMAP_ERR_INVALID_ARG, "%s: null argument", who);
@@ -305,15 +308,18 @@ static gqmap_status bm_host(const char *who, const double *A, const double *B, i
     const size_t MN = (size_t)M * N;
     const int ranks = H == 0 ? 1 : H;
     std::vector<double> Ap(AH * AW, 0.0), Bp(BH * BW, 0.0), T((size_t)M * AW), best(MN);
-    std::vector<int> bidx(MN), pick(MN * GQ_BM_HMAX);
+    std::vector<int> bidx(MN), pick(MN * GQ_BM_HMAX), last(refine ? MN : 0, -1);
+    std::vector<gq::BmNear> nbr(refine ? MN : 0);
+    std::vector<double> c0(refine ? MN : 0);
     for (int n = 0; n < N; ++n) {
         std::memcpy(&Ap[ft + AH * (n + ft)], A + (size_t)M * n, sizeof(double) * M);
         std::memcpy(&Bp[ft + U + BH * (n + ft + V)], B + (size_t)M * n, sizeof(double) * M);
     }
     const int nu = 2 * U + 1;
-    for (int r = 0; r < ranks; ++r) {
+    for (int r = 0; r < ranks + (refine ? 1 : 0); ++r) {
         std::fill(best.begin(), best.end(), INFINITY);
         std::fill(bidx.begin(), bidx.end(), -1);
+        for (gq::BmNear &q : nbr) gq::bm_near_clear(q);
         for (int v = 0; v <= 2 * V; ++v)
             for (int u = 0; u <= 2 * U; ++u) {
                 for (size_t c = 0; c < AW; ++c) {
@@ -325,11 +331,35 @@ static gqmap_status bm_host(const char *who, const double *A, const double *B, i
                 for (int n = 0; n < N; ++n)
                     for (int m = 0; m < M; ++m) {
                         const size_t o = m + (size_t)M * n;
-                        bool allowed = true;
-                        for (int j = 0; j < r; ++j) allowed = allowed && gq::bm_far(u, v, pick[o + MN * j], sep);
-                        gq::bm_keep_allowed(allowed, gq::bm_cols(&T[o], M, ft, f), u + v * nu, best[o], bidx[o]);
+                        const double c = gq::bm_cols(&T[o], M, ft, f);
+                        if (r < ranks) {
+                            bool allowed = true;
+                            for (int j = 0; j < r; ++j) allowed = allowed && gq::bm_far(u, v, pick[o + MN * j], sep);
+                            gq::bm_keep_allowed(allowed, c, u + v * nu, best[o], bidx[o]);
+                        }
+                        if (refine && r >= 1) gq::bm_capture(u, v, last[o], c, nbr[o]);
                     }
             }
+        if (refine) {
+            for (size_t o = 0; o < MN; ++o) {
+                if (r >= 1) {
+                    double out[4];
+                    gq::bm_refined(last[o], c0[o], nbr[o], U, V, out);
+                    double *fl = flow + 2 * MN * (r - 1), *cv = curv ? curv + 2 * MN * (r - 1) : nullptr;
+                    fl[o] = out[0];
+                    fl[o + MN] = out[1];
+                    if (cost) cost[o + MN * (r - 1)] = c0[o];
+                    if (cv) cv[o] = out[2], cv[o + MN] = out[3];
+                }
+                if (r < ranks) {
+                    const bool found = bidx[o] >= 0;
+                    last[o] = found ? gq::bm_pack(bidx[o] % nu, bidx[o] / nu) : -1;
+                    c0[o] = best[o];
+                    pick[o + MN * r] = found ? last[o] : pick[o + MN * (r > 0 ? r - 1 : 0)];
+                }
+            }
+            continue;
+        }
         double *fl = flow + 2 * MN * r;
         for (size_t o = 0; o < MN; ++o) {
             const bool found = bidx[o] >= 0;
@@ -348,7 +378,7 @@ extern "C" {
 gqmap_status gqmap_block_match_host(const double *A, const double *B, int M, int N, int U, int V, int ft,
                                     double sigma, double *flow, double *cost)
 {
-    return bm_host("gqmap_block_match_host", A, B, M, N, U, V, ft, sigma, 0, 1, flow, cost);
+    return bm_host("gqmap_block_match_host", A, B, M, N, U, V, ft, sigma, 0, 1, false, flow, cost, nullptr);
 }
 
 gqmap_status gqmap_block_match_multi_host(const double *A, const double *B, int M, int N, int U, int V, int ft,
@@ -357,7 +387,16 @@ gqmap_status gqmap_block_match_multi_host(const double *A, const double *B, int 
     gq::clear_error();
     const char *bad = gq::bm_bad_multi(H, sep);
     GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_multi_host: %s (H=%d sep=%d)", bad, H, sep);
-    return bm_host("gqmap_block_match_multi_host", A, B, M, N, U, V, ft, sigma, H, sep, flow, cost);
+    return bm_host("gqmap_block_match_multi_host", A, B, M, N, U, V, ft, sigma, H, sep, false, flow, cost, nullptr);
+}
+
+gqmap_status gqmap_block_match_refine_host(const double *A, const double *B, int M, int N, int U, int V, int ft,
+                                           double sigma, int H, int sep, double *flow, double *cost, double *curv)
+{
+    gq::clear_error();
+    const char *bad = gq::bm_bad_multi(H, sep);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_refine_host: %s (H=%d sep=%d)", bad, H, sep);
+    return bm_host("gqmap_block_match_refine_host", A, B, M, N, U, V, ft, sigma, H, sep, true, flow, cost, curv);
 }
 
 }  // extern "C"

@@ -97,13 +97,17 @@ def rand_uniform(seed: int, stream: int, n: int, first: int = 0) -> np.ndarray:
 
 
 def initial_state(options: dict, M: int, N: int, seed: int = 0, T: float | None = None,
-                  engine: str = "mixture", flow=None) -> State:
+                  engine: str = "mixture", flow=None, sigma=None) -> State:
     """Host copy of gqmap_init_state: gqmap_gpu_mixture.m:18-24 with the
     library RNG (what the device generates for the same seed).  With a flow
     (M x N x 2 on the node grid) the host copy of gqmap_init_state_flow:
     component 0 of the mean is the flow clamped to the range; NaN and
     |x| > 1e9 entries keep the draw.  With M x N x 2 x H the host copy of
-    gqmap_init_state_flows: component l < H takes slice l in the same way."""
+    gqmap_init_state_flows: component l < H takes slice l in the same way.
+    With sigma as well (shaped as flow, plane 0 = sigma_u, plane 1 = sigma_v)
+    the host copy of gqmap_init_state_seeded: a finite entry > 0 puts
+    min(max(x, sig_lo), sig_hi) into component l < H of sigu / sigv; NaN, <= 0
+    and Inf entries keep the draw."""
     L = int(options["L"])
     MNL = M * N * L
     sh = lambda a: a.reshape((M, N, L), order="F")
@@ -132,6 +136,20 @@ def initial_state(options: dict, M: int, N: int, seed: int = 0, T: float | None 
                 with np.errstate(invalid="ignore"):
                     known = ~(np.isnan(x) | (np.abs(x) > 1e9))
                     plane[:, :, l] = np.where(known, np.minimum(np.maximum(x, lo), hi), plane[:, :, l])
+    if sigma is not None:
+        if flow is None:
+            raise ValueError("sigma needs a flow")
+        sigma = np.asarray(sigma, dtype=np.float64)
+        if sigma.ndim == 3:
+            sigma = sigma[:, :, :, None]
+        if sigma.shape != flow.shape:
+            raise ValueError(f"sigma shape {sigma.shape} != flow shape {flow.shape}")
+        o = make_options(options, engine)
+        for l in range(sigma.shape[3]):
+            for plane, x in ((st.sigu, sigma[:, :, 0, l]), (st.sigv, sigma[:, :, 1, l])):
+                with np.errstate(invalid="ignore"):
+                    given = np.isfinite(x) & (x > 0)
+                    plane[:, :, l] = np.where(given, np.minimum(np.maximum(x, o.sig_lo), o.sig_hi), plane[:, :, l])
     return st
 
 
@@ -201,12 +219,24 @@ class Engine:
     def init_state(self, seed: int = 0) -> None:
         check(self.lib.gqmap_init_state(self.ctx, C.c_uint64(seed)), "gqmap_init_state")
 
-    def init_state_from_flow(self, flow, seed: int = 0) -> None:
+    def init_state_from_flow(self, flow, seed: int = 0, sigma=None) -> None:
         """gqmap_init_state_flow: init_state(seed) with component 0 of the mean
         set to `flow` (full node grid M x N x 2) clamped to the options' range.
         A flow M x N x 2 x H (H <= L, e.g. from block_match_init(hypotheses=H))
-        seeds components 0..H-1 from its slices (gqmap_init_state_flows)."""
+        seeds components 0..H-1 from its slices (gqmap_init_state_flows).
+        sigma (shaped as flow, e.g. from block_match_init(sigma_from_cost=True))
+        also sets sigu / sigv of those components, clamped to [sig_lo, sig_hi],
+        where it is finite and > 0 (gqmap_init_state_seeded)."""
         flow = f64(flow)
+        if sigma is not None:
+            sigma = f64(sigma)
+            if sigma.shape != flow.shape or flow.ndim not in (3, 4) or flow.shape[:3] != (self.M, self.N, 2):
+                raise ValueError(f"flow {flow.shape} and sigma {sigma.shape} must both be the node grid "
+                                 f"{(self.M, self.N, 2)} (x H)")
+            H = int(flow.shape[3]) if flow.ndim == 4 else 1
+            check(self.lib.gqmap_init_state_seeded(self.ctx, dptr(flow), dptr(sigma), H, C.c_uint64(seed)),
+                  "gqmap_init_state_seeded")
+            return
         if flow.ndim == 4 and flow.shape[:3] == (self.M, self.N, 2):
             check(self.lib.gqmap_init_state_flows(self.ctx, dptr(flow), int(flow.shape[3]), C.c_uint64(seed)),
                   "gqmap_init_state_flows")
@@ -363,7 +393,7 @@ def aepe(tflow: np.ndarray, flow: np.ndarray, unknown: np.ndarray, crop: int = 1
 
 def _solve(engine: str, options: dict, I1, I2, *, seed: int = 0, precision: str = "fp64",
            device: int = 0, state: State | None = None, verbose: bool = False,
-           eval_every: int = 300, init_flow=None):
+           eval_every: int = 300, init_flow=None, init_sigma=None):
     its = int(options["its"])
     L = int(options["L"])
     sup = engine == "super"
@@ -375,11 +405,13 @@ def _solve(engine: str, options: dict, I1, I2, *, seed: int = 0, precision: str 
     Energy = np.zeros(its)
     best = np.inf
     mark = None
+    if init_sigma is not None and init_flow is None:
+        raise ValueError("init_sigma needs init_flow")
     with Engine(options, I1, I2, engine, precision, device) as eng:
         if state is not None:
             eng.set_state(state)
         elif init_flow is not None:
-            eng.init_state_from_flow(init_flow, seed)
+            eng.init_state_from_flow(init_flow, seed, init_sigma)
         else:
             eng.init_state(seed)
         it = 1
@@ -431,7 +463,8 @@ def gqmap_gpuSuper_mix_entropy(options: dict, I1, I2, **kw):
 
 def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7,
                      engine: str = "mixture", device: int = 0, host: bool = False,
-                     hypotheses: int | None = None, sep: int = 2):
+                     hypotheses: int | None = None, sep: int = 2, subpixel: bool = False,
+                     sigma_from_cost: bool = False, lambdad: float = 1.0, sigma_min: float = 0.5):
     """A start and a range for the engines from two frames alone
     (legacy/optical_flow_temp.m:13-32; defaults: the reference's at scale 1,
     U = floor(6*scale)+1).  The engine's data term compares I1(i, j) with I2 at
@@ -448,12 +481,43 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     column-major order of the block; NaN when no pixel of the block has that
     rank).  It is not a mean: the rank-k picks of different pixels are
     unrelated modes, and averaging them would blend them into a displacement
-    that none of the pixels proposed."""
+    that none of the pixels proposed.
+
+    subpixel=True takes the flows of block_match(subpixel=True) instead (each
+    axis moved by up to half a pixel along the parabola through the pick's cost
+    and its two neighbours'), negated as above; shapes as without it.  The
+    ranges stay +-V / +-U.  sigma_from_cost=True (needs subpixel) returns
+    (flow, ranges, sigma), sigma shaped as flow, plane 0 = sigma_u, for init_sigma=
+    / Engine.init_state_from_flow(sigma=): under the engine's data term
+    -lambdad |dI| per pixel the parabola's curvature curv is a Laplace estimate
+    of the precision of the mean proposed, so sigma = max(sqrt(1 / (lambdad
+    curv)), sigma_min) where curv > 0 and NaN (keeps the draw) elsewhere.
+    sigma_min = 0.5 because a three-point fit on an integer grid cannot certify
+    less than half a pixel; it is a knob, not a measured optimum.
+    engine="super": rank 0's curvature is the SUM over the 4 x 4 block (the
+    node's data term sums its 16 pixels, and precisions add) beside the block
+    mean of the refined flows; rank k >= 1 takes flow and curvature of the one
+    cheapest pixel, by the rule above."""
     from .ops import block_match
     sup = engine == "super"
+    if sigma_from_cost and not subpixel:
+        raise ValueError("block_match_init: sigma_from_cost needs subpixel=True")
     if sup and (np.shape(I1)[0] % 4 or np.shape(I1)[1] % 4):
         raise ValueError("super engine: image size must be divisible by 4")
     ranges = dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))
+    if subpixel:
+        out, cost, curv = block_match(I1, I2, U, V, ft, sigma, device=device, host=host, hypotheses=hypotheses,
+                                      sep=sep, subpixel=True)
+        flow = np.asfortranarray(0.0 - out)
+        if sup:
+            flow, curv = _super_hypotheses(flow, cost, curv)
+        if hypotheses is None:
+            flow, curv = np.asfortranarray(flow[:, :, :, 0]), np.asfortranarray(curv[:, :, :, 0])
+        if not sigma_from_cost:
+            return flow, ranges
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sig = np.where(curv > 0, np.maximum(np.sqrt(1.0 / (float(lambdad) * curv)), float(sigma_min)), np.nan)
+        return flow, ranges, np.asfortranarray(sig)
     if hypotheses is None:
         out, _ = block_match(I1, I2, U, V, ft, sigma, device=device, host=host)
         flow = np.asfortranarray(0.0 - out)
@@ -468,9 +532,22 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     return flow, ranges
 
 
-def _super_hypotheses(flow, cost):
+def _super_hypotheses(flow, cost, curv=None):
     """Pixel hypotheses (M x N x 2 x H, M x N x H) on the super node grid; the
-    rule is in block_match_init's docstring."""
+    rule is in block_match_init's docstring.  With curv (shaped as flow) returns
+    (flow, curv) on the node grid: the block sum at rank 0, the cheapest pixel's
+    curvature at rank k >= 1 (0 when the whole block misses the rank)."""
+    if curv is not None:
+        M, N, _, H = flow.shape
+        m4, n4 = M // 4, N // 4
+        kout = np.zeros((m4, n4, 2, H), order="F")
+        kout[:, :, :, 0] = curv[:, :, :, 0].reshape(m4, 4, n4, 4, 2).sum(axis=(1, 3))
+        kb = curv.reshape(m4, 4, n4, 4, 2, H).transpose(0, 2, 3, 1, 4, 5).reshape(m4, n4, 16, 2, H)
+        cb = cost.reshape(m4, 4, n4, 4, H).transpose(0, 2, 3, 1, 4).reshape(m4, n4, 16, H)
+        for k in range(1, H):
+            first = np.argmin(cb[:, :, :, k], axis=2)
+            kout[:, :, :, k] = np.take_along_axis(kb[:, :, :, :, k], first[:, :, None, None], axis=2)[:, :, 0, :]
+        return _super_hypotheses(flow, cost), kout
     M, N, _, H = flow.shape
     m4, n4 = M // 4, N // 4
     out = np.full((m4, n4, 2, H), np.nan, order="F")

@@ -97,7 +97,8 @@ def warp_image(V, warp, fill: bool = True, device: int = 0) -> np.ndarray:
 
 
 def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, device: int = 0,
-                host: bool = False, timed: bool = False, hypotheses: int | None = None, sep: int = 2):
+                host: bool = False, timed: bool = False, hypotheses: int | None = None, sep: int = 2,
+                subpixel: bool = False):
     """legacy/optical_flow_temp.m:13-32: per pixel the displacement of the
     (2U+1) x (2V+1) window with the smallest Gaussian-filtered |A - B shifted|
     (first minimum).  Returns (flow M x N x 2 = cat(3, vmt, umt), cost M x N):
@@ -109,12 +110,23 @@ def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, d
     (gqmap_block_match_multi): flow M x N x 2 x H, cost M x N x H.  Rank 0 is
     the result above; rank k is the first minimum over the displacements at
     least `sep` away (larger of the row and column distance) from every earlier
-    pick.  A rank with no displacement left is NaN in flow and +Inf in cost."""
+    pick.  A rank with no displacement left is NaN in flow and +Inf in cost.
+
+    subpixel=True (gqmap_block_match_refine; hypotheses defaults to 1, shapes as
+    with hypotheses=) returns (flow, cost, curv): per rank and axis a three-point
+    parabola through the cost at the pick and at its two neighbours moves the
+    flow by at most half a pixel, and curv (M x N x 2 x H, laid out as flow) is
+    the parabola's second difference cm - 2 c0 + cp; an axis whose pick sits on
+    the window's edge, or is not a strict enough minimum of its three points,
+    keeps the integer flow and has curv 0.  cost stays the cost at the integer
+    pick.  A missing rank is NaN / +Inf / 0."""
     A, B = f64(A), f64(B)
     if A.ndim != 2 or A.shape != B.shape:
         raise ValueError("block_match: A and B must be equal-size 2-D images")
     M, N = A.shape
     lib = _lib.load()
+    if subpixel and hypotheses is None:
+        hypotheses = 1
     if hypotheses is not None:
         H = int(hypotheses)
         if not 1 <= H <= 4:  # the shapes below depend on it; the library checks the rest
@@ -122,6 +134,15 @@ def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, d
         flow = np.zeros((M, N, 2, H), order="F")
         cost = np.zeros((M, N, H), order="F")
         args = (dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), H, int(sep), dptr(flow), dptr(cost))
+        if subpixel:
+            curv = np.zeros((M, N, 2, H), order="F")
+            if host:
+                check(lib.gqmap_block_match_refine_host(*args, dptr(curv)), "gqmap_block_match_refine_host")
+                return (flow, cost, curv, float("nan")) if timed else (flow, cost, curv)
+            ms = C.c_double(0)
+            check(lib.gqmap_block_match_refine(*args, dptr(curv), C.cast(C.byref(ms), _lib._D) if timed else None,
+                                               device), "gqmap_block_match_refine")
+            return (flow, cost, curv, ms.value) if timed else (flow, cost, curv)
         if host:
             check(lib.gqmap_block_match_multi_host(*args), "gqmap_block_match_multi_host")
             return (flow, cost, float("nan")) if timed else (flow, cost)

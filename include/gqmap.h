@@ -165,6 +165,17 @@ gqmap_status gqmap_init_state_flow(gqmap_ctx *ctx, const double *flow, uint64_t 
  * contexts, NaN or |x| > 1e9 keep the draw); components l >= H and every other
  * plane: exactly gqmap_init_state.  gqmap_block_match_multi yields such flows. */
 gqmap_status gqmap_init_state_flows(gqmap_ctx *ctx, const double *flows, int H, uint64_t seed);
+/* gqmap_init_state_flows with a width per node as well: sigmas is the FULL
+ * node grid M x Ng x 2 x H laid out as flows, plane 0 = sigma_u, plane 1 =
+ * sigma_v.  A finite entry > 0 puts min(max(x, sig_lo), sig_hi) of the
+ * context's options into component l < H of sigu / sigv (rounded to float in
+ * fp32 contexts); NaN, <= 0 and Inf entries keep the draw.  The write reaches
+ * what the flows' write reaches (both state buffers, ghost columns, border
+ * ring).  sigmas = NULL: exactly gqmap_init_state_flows.  Everything else:
+ * exactly gqmap_init_state.  gqmap_block_match_refine's curvature yields such
+ * widths (block_match_init(sigma_from_cost=True) in the Python package). */
+gqmap_status gqmap_init_state_seeded(gqmap_ctx *ctx, const double *flows, const double *sigmas,
+                                     int H, uint64_t seed);
 gqmap_status gqmap_set_state(gqmap_ctx *ctx, const gqmap_state *st);
 gqmap_status gqmap_get_state(gqmap_ctx *ctx, gqmap_state *st);
 /* Run up to n_iter iterations (one iteration = gqmap_gpu_mixture.m:27-75
@@ -294,6 +305,26 @@ gqmap_status gqmap_block_match_multi(const double *A, const double *B, int M, in
 gqmap_status gqmap_block_match_multi_host(const double *A, const double *B, int M, int N, int U,
                                           int V, int ft, double sigma, int H, int sep,
                                           double *flow, double *cost);
+/* gqmap_block_match_multi with a sub-pixel offset and a curvature per rank.
+ * Picks, ranks, sep, missing ranks and cost (the cost c0 at the integer pick
+ * (u0, v0), bit for bit) are gqmap_block_match_multi's.  Per axis, on its own
+ * (rows: (u0 -/+ 1, v0); columns: (u0, v0 -/+ 1)), with cm, cp the filtered
+ * costs of the two neighbours, allowed by sep or not: the axis is refinable when
+ * both neighbours lie inside the window, cm >= c0, cp >= c0 and
+ * den = (cm - c0) + (cp - c0) > 0; then delta = min(max((cm - cp) / (2 den),
+ * -0.5), 0.5), else delta = 0.
+ * flow (M x N x 2 x H) = ((V - v0) - delta_v, (U - u0) - delta_u), layout and
+ * sign of gqmap_block_match_multi's; curv (M x N x 2 x H, may be NULL) = (den_v,
+ * den_u), 0 on an axis that is not refinable; cost (M x N x H, may be NULL).
+ * Missing rank: flow NaN, cost +Inf, curv 0.  One kernel, H + 1 scans of the
+ * staged tiles (the neighbour costs are computed again, no cost volume). */
+gqmap_status gqmap_block_match_refine(const double *A, const double *B, int M, int N, int U, int V,
+                                      int ft, double sigma, int H, int sep, double *flow,
+                                      double *cost, double *curv, double *elapsed_ms, int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_block_match_refine_host(const double *A, const double *B, int M, int N, int U,
+                                           int V, int ft, double sigma, int H, int sep,
+                                           double *flow, double *cost, double *curv);
 
 /* Structure-texture preprocessing: the generator of the frames
  * optical_flowSuper.m:7-14 loads with preprocessed = true (ROF decomposition by

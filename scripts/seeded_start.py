@@ -5,10 +5,14 @@ block_match_init for every start, one seed throughout.  Three starts:
   random   gqmap_init_state
   seed-1   component 0 from the block-matching argmin
   seed-3   components 0..2 from the three best separated displacements (--sep)
+  sub-3    as seed-3 with the sub-pixel flows (block_match_init(subpixel=True))
+  sub-3+s  as sub-3 with sigma of those components from the cost's curvature
+           (sigma_from_cost=True, lambdad of the options, --sigma-min)
 AEPE (against the .flo ground truth, which no start sees) and Energy at
-iterations 1, 300, 600, ... (profiles/block_match_multi_start.txt).
+iterations 1, 300, 600, ... (profiles/block_match_multi_start.txt for the
+first three, profiles/block_match_refine_start.txt with all five).
 
-usage: seeded_start.py [--its 3000] [--every 300] [--seed 0] [--sep 2] [--pair rubberwhale]"""
+usage: seeded_start.py [--its 3000] [--every 300] [--seed 0] [--sep 2] [--sigma-min 0.5] [--pair rubberwhale]"""
 import argparse
 import os
 import sys
@@ -24,6 +28,7 @@ ap.add_argument("--its", type=int, default=3000)
 ap.add_argument("--every", type=int, default=300)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--sep", type=int, default=2)
+ap.add_argument("--sigma-min", type=float, default=0.5)
 ap.add_argument("--pair", default="rubberwhale")
 a = ap.parse_args()
 
@@ -32,15 +37,25 @@ _, flo, _, unk = flow_to_color(gt)
 flow3, ranges = block_match_init(I1, I2, hypotheses=3, sep=a.sep)
 flow1, _ = block_match_init(I1, I2)
 assert np.array_equal(flow1, flow3[..., 0])
+sub3, _, sig3 = block_match_init(I1, I2, hypotheses=3, sep=a.sep, subpixel=True, sigma_from_cost=True, lambdad=1.0,
+                                 sigma_min=a.sigma_min)
 opts = dict(trueFlow=flo, unknownIdx=unk, its=a.its, K=9, L=3, temperature=0.0, drate=0.5, epsn=0.001 ** 2,
             lambdas=5.0, lambdad=1.0, **ranges)
 M, N = I1.shape
 print(f"{a.pair} {M}x{N} mixture L=3 K=9 lambdas=5 lambdad=1 fp64, range {ranges}, seed {a.seed}, sep {a.sep}; "
       f"{int(np.isnan(flow3[:, :, 0, 1:]).sum())} missing rank entries", flush=True)
+known = ~np.asarray(unk, dtype=bool)
+for name, f in (("integer", flow1), ("sub-pixel", sub3[..., 0])):
+    print(f"raw rank-0 {name} flow: known-pixel AEPE {np.sqrt(np.sum((flo - f) ** 2, axis=2))[known].mean():.5f}")
+print(f"sigma from the cost (floor {a.sigma_min}): {100 * np.isnan(sig3).mean():.2f}% not refinable (keep the draw), "
+      f"{100 * np.mean(sig3[~np.isnan(sig3)] == a.sigma_min):.1f}% of the rest at the floor, percentiles 1/50/99 "
+      + "/".join(f"{x:.3f}" for x in np.nanpercentile(sig3, (1, 50, 99))), flush=True)
 marks = [1] + list(range(a.every, a.its + 1, a.every))
 rows = {}
-for name, init in (("random", None), ("seed-1", flow1), ("seed-3", flow3)):
-    _, _, _, AEPE, Energy, _ = gqmap_gpu_mixture(opts, I1, I2, seed=a.seed, init_flow=init, eval_every=a.every)
+for name, init, sig in (("random", None, None), ("seed-1", flow1, None), ("seed-3", flow3, None),
+                        ("sub-3", sub3, None), ("sub-3+s", sub3, sig3)):
+    _, _, _, AEPE, Energy, _ = gqmap_gpu_mixture(opts, I1, I2, seed=a.seed, init_flow=init, init_sigma=sig,
+                                                 eval_every=a.every)
     rows[name] = (AEPE, Energy)
     print(f"{name}: done", flush=True)
 print(f"{'it':>5s} " + " ".join(f"{n + ' AEPE':>12s} {n + ' Energy':>16s}" for n in rows))

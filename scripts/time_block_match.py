@@ -8,10 +8,13 @@ multiply, add) in the row pass + (2ft+1) x (multiply, add) in the column pass
 
 --hypotheses H times gqmap_block_match_multi (H ranks, separation --sep)
 instead; its flops are H times the single pass (the exclusion test is integer
-work and not counted).
+work and not counted).  --subpixel times gqmap_block_match_refine (H ranks,
+default 1): H + 1 scans, so the expectation is (H + 1) / H of the multi time at
+the same H; the flops counted are those of the H + 1 scans
+(profiles/block_match_refine_times.txt).
 
 usage: time_block_match.py [--scale S] [--U U] [--V V] [--ft FT] [--sigma SG] [--runs R] [--cols 0|8|16|32]
-                           [--hypotheses H] [--sep S]
+                           [--hypotheses H] [--sep S] [--subpixel]
   issue cases: (a) --scale 1 --U 7;  (b) --scale 4 --U 25"""
 import argparse
 import ctypes as C
@@ -39,6 +42,7 @@ ap.add_argument("--settle", type=float, default=0.5)
 ap.add_argument("--cols", type=int, default=0, help="force the tile width (0: the library's choice)")
 ap.add_argument("--hypotheses", type=int, default=None, help="H ranks through gqmap_block_match_multi")
 ap.add_argument("--sep", type=int, default=2)
+ap.add_argument("--subpixel", action="store_true", help="gqmap_block_match_refine: H + 1 scans")
 a = ap.parse_args()
 V = a.U if a.V is None else a.V
 
@@ -53,7 +57,8 @@ assert f(a.cols) == 0
 
 
 def call():
-    return block_match(I1, I2, a.U, V, a.ft, a.sigma, timed=True, hypotheses=a.hypotheses, sep=a.sep)[-1]
+    return block_match(I1, I2, a.U, V, a.ft, a.sigma, timed=True, hypotheses=a.hypotheses, sep=a.sep,
+                       subpixel=a.subpixel)[-1]
 
 
 t0, warm = time.perf_counter(), []
@@ -61,8 +66,11 @@ while not warm or time.perf_counter() - t0 < a.settle:
     warm.append(call())
 ms = [call() for _ in range(a.runs)]
 med = statistics.median(ms)
-flops = float(M) * N * (2 * a.U + 1) * (2 * V + 1) * (2 * a.ft + 1) * 5 * (a.hypotheses or 1)
+scans = (a.hypotheses or 1) + (1 if a.subpixel else 0)
+flops = float(M) * N * (2 * a.U + 1) * (2 * V + 1) * (2 * a.ft + 1) * 5 * scans
 what = "block_match" if a.hypotheses is None else f"block_match_multi H={a.hypotheses} sep={a.sep}"
+if a.subpixel:
+    what = f"block_match_refine H={a.hypotheses or 1} sep={a.sep}"
 print(f"{what} {M}x{N} U={a.U} V={V} ft={a.ft} sigma={a.sigma} cols={a.cols or 'auto'}: "
       f"warm-up {len(warm)} calls (first {warm[0]:.3f} ms), runs " + " ".join(f"{x:.3f}" for x in ms) +
       f" ms, median {med:.3f} ms, {flops / 1e9:.2f} GFLOP, {flops / (med * 1e-3) / 1e12:.2f} TF/s = "
