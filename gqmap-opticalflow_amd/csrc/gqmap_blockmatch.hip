@@ -5,12 +5,30 @@
 //
 // One workgroup of 256 lanes owns a 32 x TN output tile (rows x columns, TN =
 // 8, 16 or 32).  It stages the A tile (halo ft) and the B window (halo ft+U
-// rows, ft+V columns) in LDS once, zero outside the frame, then loops over the
+// rows, ft+V columns) in LDS once, zero outside the frame, then scans the
 // displacements: row pass of the abs-difference into an LDS tile T (32 x
 // (TN+2ft), double-buffered so one barrier per displacement is enough), column
 // pass out of T, running (min, index) in registers.  The cost volume never
 // exists in device memory.  Lanes run along m (the fastest index): global
 // loads, the final stores and every LDS access are unit-stride over a wave half.
+//
+// One kernel template, three modes (gqmap_blockmatch.h has their rules):
+//   single  1 scan; stores the argmin's flow and cost.
+//   multi   H scans ("Several hypotheses").  Every lane builds T at every
+//           displacement; only its own keep is gated by the distance to its
+//           earlier picks, which stay in registers packed (u, v), one per rank
+//           and output column.  Scan r stores rank r's flow and cost.
+//   refine  H + 1 scans ("Sub-pixel refinement").  The neighbour costs of a
+//           pick are known only once its scan has ended and the cost volume
+//           does not exist, so they are computed again: scan r < H selects
+//           rank r as multi does; scan r >= 1 also keeps the cost of every
+//           displacement one step on an axis from rank r - 1's pick
+//           (bm_capture: four integer compares per output column and
+//           displacement, 4 NPT doubles in registers) and stores rank r - 1's
+//           flow, cost and curvature.  The last scan selects nothing.
+// The mode is a template parameter, not an argument: the refine kernel at TN =
+// 32 fills the 128 VGPRs that still give bm_choose_cols its four workgroups per
+// CU, and the single kernel must not carry the ranked kernels' registers.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,6 +42,8 @@ constexpr int BM_TM = 32;        // tile rows = lanes along m
 constexpr int BM_GROUPS = 8;     // column groups of a 256-lane workgroup
 constexpr int BM_THREADS = BM_TM * BM_GROUPS;
 
+enum BmMode { BM_SINGLE, BM_MULTI, BM_REFINE };
+
 // LDS doubles of one workgroup: A tile, B window, two T tiles
 static size_t bm_lds_doubles(int TN, int U, int V, int ft)
 {
@@ -31,92 +51,19 @@ static size_t bm_lds_doubles(int TN, int U, int V, int ft)
     return AH * AW + (AH + 2 * U) * (AW + 2 * V) + 2 * (size_t)BM_TM * AW;
 }
 
-template <int NPT>  // output columns per lane: TN = 8 * NPT
+// NPT = output columns per lane: TN = 8 * NPT.  The single mode ignores H, sep
+// and curv; multi ignores curv.  cost may be null, and so may curv.
+template <int NPT, int MODE>
 __global__ __launch_bounds__(BM_THREADS) void k_block_match(const double *__restrict__ A,
                                                             const double *__restrict__ B, int M, int N, int U,
-                                                            int V, int ft, BmFilter f, int tiles_m,
-                                                            double *__restrict__ flow, double *__restrict__ cost)
+                                                            int V, int ft, BmFilter f, int tiles_m, int H, int sep,
+                                                            double *__restrict__ flow, double *__restrict__ cost,
+                                                            double *__restrict__ curv)
 {
     extern __shared__ double bm_lds[];
     constexpr int TN = BM_GROUPS * NPT;
-    const int AH = BM_TM + 2 * ft, AW = TN + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
-    double *As = bm_lds, *Bs = As + AH * AW, *Ts = Bs + BH * BW;
-    const int tid = threadIdx.x;
-    const int m0 = (int)(blockIdx.x % tiles_m) * BM_TM, n0 = (int)(blockIdx.x / tiles_m) * TN;
-
-    for (int t = tid; t < AH * AW; t += BM_THREADS) {
-        const int gm = m0 - ft + t % AH, gn = n0 - ft + t / AH;
-        As[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? A[gm + (int64_t)M * gn] : 0.0;
-    }
-    for (int t = tid; t < BH * BW; t += BM_THREADS) {
-        const int gm = m0 - ft - U + t % BH, gn = n0 - ft - V + t / BH;
-        Bs[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? B[gm + (int64_t)M * gn] : 0.0;
-    }
-    __syncthreads();
-
-    const int lm = tid % BM_TM, cg = tid / BM_TM;
-    double best[NPT];
-    int bidx[NPT];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        best[k] = INFINITY;
-        bidx[k] = 0;
-    }
-    const int nu = 2 * U + 1, nd = nu * (2 * V + 1);
-    int u = 0, v = 0;
-    for (int idx = 0; idx < nd; ++idx) {
-        double *T = Ts + (idx & 1) * (BM_TM * AW);
-        for (int c = cg; c < AW; c += BM_GROUPS) {
-            const int gn = n0 - ft + c;
-            T[lm + BM_TM * c] = bm_rows(As + lm + AH * c, Bs + (lm + u) + BH * (c + v), ft, f, m0 + lm - ft, M,
-                                        gn >= 0 && gn < N);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < NPT; ++k)
-            bm_keep(bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f), idx, best[k], bidx[k]);
-        if (++u == nu) {
-            u = 0;
-            ++v;
-        }
-    }
-
-    const int64_t MN = (int64_t)M * N;
-    const int gm = m0 + lm;
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int gn = n0 + cg + BM_GROUPS * k;
-        if (gm < M && gn < N) {
-            const int64_t o = gm + (int64_t)M * gn;
-            flow[o] = (double)(V - bidx[k] / nu);       // vmt
-            flow[o + MN] = (double)(U - bidx[k] % nu);  // umt
-            if (cost) cost[o] = best[k];
-        }
-    }
-}
-
-// H hypotheses per pixel (gqmap_blockmatch.h, "Several hypotheses"): the tiles
-// are staged once, then the displacement loop of k_block_match runs once per
-// rank over them.  Every lane builds T at every displacement; only its own
-// bm_keep is gated by the distance to its earlier picks, which stay in
-// registers packed (u, v), one per rank and output column (the rank loop is
-// unrolled over the compile-time bound GQ_BM_HMAX, so no index is dynamic).
-// Each rank's flow and cost leave for memory at the end of its pass.
-// T's buffer parity runs on a counter over ALL passes, not on idx: a pass has
-// an odd number of displacements, so idx & 1 would put the last T of a pass
-// and the first of the next into one buffer, with no barrier between a slow
-// wave's column pass and a fast wave's row pass.  With the running counter
-// consecutive displacements alternate throughout and the one barrier per
-// displacement covers the pass boundary like any other step.
-template <int NPT>
-__global__ __launch_bounds__(BM_THREADS) void k_block_match_multi(const double *__restrict__ A,
-                                                                  const double *__restrict__ B, int M, int N, int U,
-                                                                  int V, int ft, BmFilter f, int tiles_m, int H,
-                                                                  int sep, double *__restrict__ flow,
-                                                                  double *__restrict__ cost)
-{
-    extern __shared__ double bm_lds[];
-    constexpr int TN = BM_GROUPS * NPT;
+    constexpr bool RANKED = MODE != BM_SINGLE, REFINE = MODE == BM_REFINE;
+    constexpr int MAX_SCANS = !RANKED ? 1 : REFINE ? GQ_BM_HMAX + 1 : GQ_BM_HMAX;
     const int AH = BM_TM + 2 * ft, AW = TN + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
     double *As = bm_lds, *Bs = As + AH * AW, *Ts = Bs + BH * BW;
     const int tid = threadIdx.x;
@@ -134,19 +81,32 @@ __global__ __launch_bounds__(BM_THREADS) void k_block_match_multi(const double *
 
     const int lm = tid % BM_TM, cg = tid / BM_TM;
     const int nu = 2 * U + 1, nd = nu * (2 * V + 1);
+    const int scans = !RANKED ? 1 : REFINE ? H + 1 : H;
     const int64_t MN = (int64_t)M * N;
     const int gm = m0 + lm;
-    int pick[NPT][GQ_BM_HMAX - 1];
-    unsigned done = 0;  // displacements of all passes so far: T's buffer parity
+    // ranked modes: the earlier picks.  refine: rank r - 1's pick (-1 when that rank is missing), its cost, and
+    // its neighbour costs, filled during scan r
+    [[maybe_unused]] int pick[NPT][GQ_BM_HMAX - 1], last[NPT];
+    [[maybe_unused]] double c0[NPT];
+    [[maybe_unused]] BmNear nbr[NPT];
+    // T's buffer parity runs on a counter over the displacements of ALL scans, not on idx: a scan has an odd
+    // number of displacements, so idx & 1 would put the last T of a scan and the first of the next into one
+    // buffer, with no barrier between a slow wave's column pass and a fast wave's row pass.  With the running
+    // counter consecutive displacements alternate throughout and the one barrier per displacement covers the scan
+    // boundary like any other step.  (In the single mode the counter is idx.)
+    unsigned done = 0;
+    // unrolled over the compile-time bound, so no index into pick is dynamic; the break is block-uniform and every
+    // lane reaches every barrier
 #pragma unroll
-    for (int r = 0; r < GQ_BM_HMAX; ++r) {
-        if (r >= H) break;
+    for (int r = 0; r < MAX_SCANS; ++r) {
+        if (r >= scans) break;
         double best[NPT];
         int bidx[NPT];
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             best[k] = INFINITY;
-            bidx[k] = -1;
+            bidx[k] = RANKED ? -1 : 0;
+            if constexpr (REFINE) bm_near_clear(nbr[k]);
         }
         int u = 0, v = 0;
         for (int idx = 0; idx < nd; ++idx, ++done) {
@@ -159,111 +119,29 @@ __global__ __launch_bounds__(BM_THREADS) void k_block_match_multi(const double *
             __syncthreads();
 #pragma unroll
             for (int k = 0; k < NPT; ++k) {
-                bool allowed = true;
-#pragma unroll
-                for (int j = 0; j < GQ_BM_HMAX - 1; ++j)
-                    if (j < r) allowed = allowed && bm_far(u, v, pick[k][j], sep);
-                bm_keep_allowed(allowed, bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f), idx, best[k],
-                                bidx[k]);
-            }
-            if (++u == nu) {
-                u = 0;
-                ++v;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const int gn = n0 + cg + BM_GROUPS * k;
-            const bool found = bidx[k] >= 0;
-            if (gm < M && gn < N) {
-                const int64_t o = gm + (int64_t)M * gn;
-                flow[o + 2 * MN * r] = found ? (double)(V - bidx[k] / nu) : bm_nan();       // vmt
-                flow[o + 2 * MN * r + MN] = found ? (double)(U - bidx[k] % nu) : bm_nan();  // umt
-                if (cost) cost[o + MN * r] = best[k];
-            }
-            // a missing rank adds no exclusion: the allowed set stays empty for the later ranks
-            if (r < GQ_BM_HMAX - 1)
-                pick[k][r < GQ_BM_HMAX - 1 ? r : 0] =
-                    found ? bm_pack(bidx[k] % nu, bidx[k] / nu) : pick[k][r > 0 ? r - 1 : 0];
-        }
-    }
-}
-
-// H hypotheses with a sub-pixel offset and a curvature each (gqmap_blockmatch.h,
-// "Sub-pixel refinement").  The neighbour costs of a pick are known only once
-// its scan has ended and the cost volume does not exist, so they are computed
-// again: H + 1 scans over the staged tiles.  Scan r < H selects the pick of rank
-// r exactly as k_block_match_multi does; scan r >= 1 also keeps the cost of
-// every displacement that is one step on an axis from rank r - 1's pick
-// (bm_capture: four integer compares per output column and displacement, 4 NPT
-// doubles in registers).  Rank r - 1's flow, cost and curvature leave for
-// memory at the end of scan r; the last scan selects nothing.  T's buffer
-// parity runs on the counter over all scans, for the reason given above.
-template <int NPT>
-__global__ __launch_bounds__(BM_THREADS) void k_block_match_refine(const double *__restrict__ A,
-                                                                   const double *__restrict__ B, int M, int N, int U,
-                                                                   int V, int ft, BmFilter f, int tiles_m, int H,
-                                                                   int sep, double *__restrict__ flow,
-                                                                   double *__restrict__ cost,
-                                                                   double *__restrict__ curv)
-{
-    extern __shared__ double bm_lds[];
-    constexpr int TN = BM_GROUPS * NPT;
-    const int AH = BM_TM + 2 * ft, AW = TN + 2 * ft, BH = AH + 2 * U, BW = AW + 2 * V;
-    double *As = bm_lds, *Bs = As + AH * AW, *Ts = Bs + BH * BW;
-    const int tid = threadIdx.x;
-    const int m0 = (int)(blockIdx.x % tiles_m) * BM_TM, n0 = (int)(blockIdx.x / tiles_m) * TN;
-
-    for (int t = tid; t < AH * AW; t += BM_THREADS) {
-        const int gm = m0 - ft + t % AH, gn = n0 - ft + t / AH;
-        As[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? A[gm + (int64_t)M * gn] : 0.0;
-    }
-    for (int t = tid; t < BH * BW; t += BM_THREADS) {
-        const int gm = m0 - ft - U + t % BH, gn = n0 - ft - V + t / BH;
-        Bs[t] = gm >= 0 && gm < M && gn >= 0 && gn < N ? B[gm + (int64_t)M * gn] : 0.0;
-    }
-    __syncthreads();
-
-    const int lm = tid % BM_TM, cg = tid / BM_TM;
-    const int nu = 2 * U + 1, nd = nu * (2 * V + 1);
-    const int64_t MN = (int64_t)M * N;
-    const int gm = m0 + lm;
-    int pick[NPT][GQ_BM_HMAX - 1];
-    int last[NPT];     // rank r - 1's pick, -1 when that rank is missing
-    double c0[NPT];    // its cost
-    BmNear nbr[NPT];  // its neighbour costs, filled during scan r
-    unsigned done = 0;  // displacements of all scans so far: T's buffer parity
-#pragma unroll
-    for (int r = 0; r <= GQ_BM_HMAX; ++r) {
-        if (r > H) break;
-        double best[NPT];
-        int bidx[NPT];
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            best[k] = INFINITY;
-            bidx[k] = -1;
-            bm_near_clear(nbr[k]);
-        }
-        int u = 0, v = 0;
-        for (int idx = 0; idx < nd; ++idx, ++done) {
-            double *T = Ts + (done & 1u) * (BM_TM * AW);
-            for (int c = cg; c < AW; c += BM_GROUPS) {
-                const int gn = n0 - ft + c;
-                T[lm + BM_TM * c] = bm_rows(As + lm + AH * c, Bs + (lm + u) + BH * (c + v), ft, f, m0 + lm - ft, M,
-                                            gn >= 0 && gn < N);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) {
-                const double c = bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f);
-                if (r < H) {
+                if constexpr (MODE == BM_SINGLE) {
+                    bm_keep(bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f), idx, best[k], bidx[k]);
+                } else if constexpr (MODE == BM_MULTI) {
+                    // the exclusion test before the column pass: integer work on registers, which the compiler
+                    // then places ahead of the barrier.  refine below has the other order.  Each is the order
+                    // its mode was timed with; one order for both was slower in one of them.
                     bool allowed = true;
 #pragma unroll
                     for (int j = 0; j < GQ_BM_HMAX - 1; ++j)
                         if (j < r) allowed = allowed && bm_far(u, v, pick[k][j], sep);
-                    bm_keep_allowed(allowed, c, idx, best[k], bidx[k]);
+                    bm_keep_allowed(allowed, bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f), idx, best[k],
+                                    bidx[k]);
+                } else {
+                    const double c = bm_cols(T + lm + BM_TM * (cg + BM_GROUPS * k), BM_TM, ft, f);
+                    if (r < H) {
+                        bool allowed = true;
+#pragma unroll
+                        for (int j = 0; j < GQ_BM_HMAX - 1; ++j)
+                            if (j < r) allowed = allowed && bm_far(u, v, pick[k][j], sep);
+                        bm_keep_allowed(allowed, c, idx, best[k], bidx[k]);
+                    }
+                    if (r >= 1) bm_capture(u, v, last[k], c, nbr[k]);
                 }
-                if (r >= 1) bm_capture(u, v, last[k], c, nbr[k]);
             }
             if (++u == nu) {
                 u = 0;
@@ -273,24 +151,34 @@ __global__ __launch_bounds__(BM_THREADS) void k_block_match_refine(const double 
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const int gn = n0 + cg + BM_GROUPS * k;
-            if (r >= 1 && gm < M && gn < N) {
-                const int64_t o = gm + (int64_t)M * gn + 2 * MN * (r - 1);
-                double out[4];
-                bm_refined(last[k], c0[k], nbr[k], U, V, out);
-                flow[o] = out[0];
-                flow[o + MN] = out[1];
-                if (cost) cost[gm + (int64_t)M * gn + MN * (r - 1)] = c0[k];
-                if (curv) {
-                    curv[o] = out[2];
-                    curv[o + MN] = out[3];
+            const bool inside = gm < M && gn < N, found = !RANKED || bidx[k] >= 0;
+            const int64_t o = gm + (int64_t)M * gn;
+            if constexpr (REFINE) {
+                if (r >= 1 && inside) {  // rank r - 1, its neighbour costs now known
+                    double out[4];
+                    bm_refined(last[k], c0[k], nbr[k], U, V, out);
+                    flow[o + 2 * MN * (r - 1)] = out[0];
+                    flow[o + 2 * MN * (r - 1) + MN] = out[1];
+                    if (cost) cost[o + MN * (r - 1)] = c0[k];
+                    if (curv) {
+                        curv[o + 2 * MN * (r - 1)] = out[2];
+                        curv[o + 2 * MN * (r - 1) + MN] = out[3];
+                    }
                 }
+            } else if (inside) {  // rank r
+                flow[o + 2 * MN * r] = found ? (double)(V - bidx[k] / nu) : bm_nan();       // vmt
+                flow[o + 2 * MN * r + MN] = found ? (double)(U - bidx[k] % nu) : bm_nan();  // umt
+                if (cost) cost[o + MN * r] = best[k];
             }
-            const bool found = bidx[k] >= 0;
-            last[k] = found ? bm_pack(bidx[k] % nu, bidx[k] / nu) : -1;
-            c0[k] = best[k];
-            // a missing rank adds no exclusion: the allowed set stays empty for the later ranks
-            if (r < GQ_BM_HMAX - 1)
-                pick[k][r < GQ_BM_HMAX - 1 ? r : 0] = found ? last[k] : pick[k][r > 0 ? r - 1 : 0];
+            if constexpr (RANKED) {  // this scan's pick, for the scans after it
+                const int p = found ? bm_pack(bidx[k] % nu, bidx[k] / nu) : -1;
+                if constexpr (REFINE) {
+                    last[k] = p;
+                    c0[k] = best[k];
+                }
+                // a missing rank adds no exclusion: the allowed set stays empty for the later ranks
+                if (r < GQ_BM_HMAX - 1) pick[k][r < GQ_BM_HMAX - 1 ? r : 0] = found ? p : pick[k][r > 0 ? r - 1 : 0];
+            }
         }
     }
 }
@@ -322,31 +210,24 @@ static int bm_choose_cols(int M, int N, int U, int V, int ft, int cus)
 // tile columns forced by gqmap_debug_block_match_cols (0: chosen from the grid)
 static int g_bm_cols = 0;
 
-// H = 0: the single-hypothesis kernel k_block_match (gqmap_block_match); H >= 1: k_block_match_multi, or
-// with refine k_block_match_refine (dcurv may be null)
+// H = 0: the single mode (gqmap_block_match); H >= 1: multi, or with refine the refine mode (dcurv may be null)
 template <int NPT>
 static hipError_t bm_launch(const double *dA, const double *dB, int M, int N, int U, int V, int ft,
                             const BmFilter &f, int H, int sep, bool refine, double *dflow, double *dcost,
                             double *dcurv, hipStream_t s)
 {
     constexpr int TN = BM_GROUPS * NPT;
+    const auto kernel = H == 0   ? &k_block_match<NPT, BM_SINGLE>
+                        : refine ? &k_block_match<NPT, BM_REFINE>
+                                 : &k_block_match<NPT, BM_MULTI>;
     const size_t bytes = bm_lds_doubles(TN, U, V, ft) * sizeof(double);
     // above 64 KB (up to 117 KB at U = V = 32, ft = 4, TN = 32) the dynamic LDS limit must be raised
-    hipError_t e = hipFuncSetAttribute(H == 0   ? reinterpret_cast<const void *>(&k_block_match<NPT>)
-                                       : refine ? reinterpret_cast<const void *>(&k_block_match_refine<NPT>)
-                                                : reinterpret_cast<const void *>(&k_block_match_multi<NPT>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
     const int tiles_m = (M + BM_TM - 1) / BM_TM, tiles_n = (N + TN - 1) / TN;
     const dim3 grid((unsigned)((int64_t)tiles_m * tiles_n)), block(BM_THREADS);
-    if (H == 0)
-        k_block_match<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, dflow, dcost);
-    else if (refine)
-        k_block_match_refine<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, H, sep, dflow,
-                                                             dcost, dcurv);
-    else
-        k_block_match_multi<NPT><<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, H, sep, dflow,
-                                                            dcost);
+    kernel<<<grid, block, bytes, s>>>(dA, dB, M, N, U, V, ft, f, tiles_m, H, sep, dflow, dcost, dcurv);
     return hipGetLastError();
 }
 

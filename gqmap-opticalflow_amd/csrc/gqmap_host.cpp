@@ -340,34 +340,33 @@ static gqmap_status bm_host(const char *who, const double *A, const double *B, i
                         if (refine && r >= 1) gq::bm_capture(u, v, last[o], c, nbr[o]);
                     }
             }
-        if (refine) {
-            for (size_t o = 0; o < MN; ++o) {
-                if (r >= 1) {
-                    double out[4];
-                    gq::bm_refined(last[o], c0[o], nbr[o], U, V, out);
-                    double *fl = flow + 2 * MN * (r - 1), *cv = curv ? curv + 2 * MN * (r - 1) : nullptr;
-                    fl[o] = out[0];
-                    fl[o + MN] = out[1];
-                    if (cost) cost[o + MN * (r - 1)] = c0[o];
-                    if (cv) cv[o] = out[2], cv[o + MN] = out[3];
-                }
-                if (r < ranks) {
-                    const bool found = bidx[o] >= 0;
-                    last[o] = found ? gq::bm_pack(bidx[o] % nu, bidx[o] / nu) : -1;
-                    c0[o] = best[o];
-                    pick[o + MN * r] = found ? last[o] : pick[o + MN * (r > 0 ? r - 1 : 0)];
-                }
-            }
-            continue;
-        }
-        double *fl = flow + 2 * MN * r;
         for (size_t o = 0; o < MN; ++o) {
             const bool found = bidx[o] >= 0;
-            fl[o] = found ? (double)(V - bidx[o] / nu) : gq::bm_nan();       // vmt
-            fl[o + MN] = found ? (double)(U - bidx[o] % nu) : gq::bm_nan();  // umt
-            if (cost) cost[o + MN * r] = best[o];
+            if (refine) {
+                if (r >= 1) {  // rank r - 1, its neighbour costs now known
+                    double out[4];
+                    gq::bm_refined(last[o], c0[o], nbr[o], U, V, out);
+                    flow[o + 2 * MN * (r - 1)] = out[0];
+                    flow[o + 2 * MN * (r - 1) + MN] = out[1];
+                    if (cost) cost[o + MN * (r - 1)] = c0[o];
+                    if (curv) {
+                        curv[o + 2 * MN * (r - 1)] = out[2];
+                        curv[o + 2 * MN * (r - 1) + MN] = out[3];
+                    }
+                }
+            } else {  // rank r
+                flow[o + 2 * MN * r] = found ? (double)(V - bidx[o] / nu) : gq::bm_nan();       // vmt
+                flow[o + 2 * MN * r + MN] = found ? (double)(U - bidx[o] % nu) : gq::bm_nan();  // umt
+                if (cost) cost[o + MN * r] = best[o];
+            }
+            // this scan's pick, for the scans after it
+            const int p = found ? gq::bm_pack(bidx[o] % nu, bidx[o] / nu) : -1;
+            if (refine) {
+                last[o] = p;
+                c0[o] = best[o];
+            }
             // a missing rank adds no exclusion: the allowed set stays empty for the later ranks
-            pick[o + MN * r] = found ? gq::bm_pack(bidx[o] % nu, bidx[o] / nu) : pick[o + MN * (r > 0 ? r - 1 : 0)];
+            if (r < ranks) pick[o + MN * r] = found ? p : pick[o + MN * (r > 0 ? r - 1 : 0)];
         }
     }
     return GQMAP_OK;

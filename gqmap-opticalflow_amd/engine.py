@@ -505,31 +505,23 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     if sup and (np.shape(I1)[0] % 4 or np.shape(I1)[1] % 4):
         raise ValueError("super engine: image size must be divisible by 4")
     ranges = dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))
-    if subpixel:
-        out, cost, curv = block_match(I1, I2, U, V, ft, sigma, device=device, host=host, hypotheses=hypotheses,
-                                      sep=sep, subpixel=True)
-        flow = np.asfortranarray(0.0 - out)
-        if sup:
-            flow, curv = _super_hypotheses(flow, cost, curv)
-        if hypotheses is None:
-            flow, curv = np.asfortranarray(flow[:, :, :, 0]), np.asfortranarray(curv[:, :, :, 0])
-        if not sigma_from_cost:
-            return flow, ranges
-        with np.errstate(divide="ignore", invalid="ignore"):
-            sig = np.where(curv > 0, np.maximum(np.sqrt(1.0 / (float(lambdad) * curv)), float(sigma_min)), np.nan)
-        return flow, ranges, np.asfortranarray(sig)
-    if hypotheses is None:
-        out, _ = block_match(I1, I2, U, V, ft, sigma, device=device, host=host)
-        flow = np.asfortranarray(0.0 - out)
-        if sup:
-            M, N = flow.shape[:2]
-            flow = np.asfortranarray(flow.reshape(M // 4, 4, N // 4, 4, 2).mean(axis=(1, 3)))
-        return flow, ranges
-    out, cost = block_match(I1, I2, U, V, ft, sigma, device=device, host=host, hypotheses=hypotheses, sep=sep)
-    flow = np.asfortranarray(0.0 - out)
+    out, cost, *curv = block_match(I1, I2, U, V, ft, sigma, device=device, host=host, hypotheses=hypotheses, sep=sep,
+                                   subpixel=subpixel)
+    flow, curv = np.asfortranarray(0.0 - out), curv[0] if subpixel else None
+    if flow.ndim == 3:  # without hypotheses or subpixel block_match leaves the rank axis out
+        flow, cost = flow[..., None], cost[..., None]
     if sup:
-        flow = _super_hypotheses(flow, cost)
-    return flow, ranges
+        nodes = _super_hypotheses(flow, cost, curv)
+        flow, curv = nodes if subpixel else (nodes, None)
+    if hypotheses is None:
+        flow = np.asfortranarray(flow[:, :, :, 0])
+    if not sigma_from_cost:
+        return flow, ranges
+    if hypotheses is None:
+        curv = curv[:, :, :, 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sig = np.where(curv > 0, np.maximum(np.sqrt(1.0 / (float(lambdad) * curv)), float(sigma_min)), np.nan)
+    return flow, ranges, np.asfortranarray(sig)
 
 
 def _super_hypotheses(flow, cost, curv=None):
@@ -537,26 +529,18 @@ def _super_hypotheses(flow, cost, curv=None):
     rule is in block_match_init's docstring.  With curv (shaped as flow) returns
     (flow, curv) on the node grid: the block sum at rank 0, the cheapest pixel's
     curvature at rank k >= 1 (0 when the whole block misses the rank)."""
-    if curv is not None:
-        M, N, _, H = flow.shape
-        m4, n4 = M // 4, N // 4
-        kout = np.zeros((m4, n4, 2, H), order="F")
-        kout[:, :, :, 0] = curv[:, :, :, 0].reshape(m4, 4, n4, 4, 2).sum(axis=(1, 3))
-        kb = curv.reshape(m4, 4, n4, 4, 2, H).transpose(0, 2, 3, 1, 4, 5).reshape(m4, n4, 16, 2, H)
-        cb = cost.reshape(m4, 4, n4, 4, H).transpose(0, 2, 3, 1, 4).reshape(m4, n4, 16, H)
-        for k in range(1, H):
-            first = np.argmin(cb[:, :, :, k], axis=2)
-            kout[:, :, :, k] = np.take_along_axis(kb[:, :, :, :, k], first[:, :, None, None], axis=2)[:, :, 0, :]
-        return _super_hypotheses(flow, cost), kout
     M, N, _, H = flow.shape
     m4, n4 = M // 4, N // 4
-    out = np.full((m4, n4, 2, H), np.nan, order="F")
-    out[:, :, :, 0] = flow[:, :, :, 0].reshape(m4, 4, n4, 4, 2).mean(axis=(1, 3))
     # block pixels in column-major order of the block: index i + 4 j
-    fb = flow.reshape(m4, 4, n4, 4, 2, H).transpose(0, 2, 3, 1, 4, 5).reshape(m4, n4, 16, 2, H)
     cb = cost.reshape(m4, 4, n4, 4, H).transpose(0, 2, 3, 1, 4).reshape(m4, n4, 16, H)
-    for k in range(1, H):
-        first = np.argmin(cb[:, :, :, k], axis=2)  # +Inf (missing) never beats a finite cost; first on ties
-        pick = np.take_along_axis(fb[:, :, :, :, k], first[:, :, None, None], axis=2)[:, :, 0, :]
-        out[:, :, :, k] = pick  # NaN already when the whole block misses the rank
-    return out
+    first = np.argmin(cb, axis=2)  # +Inf (missing) never beats a finite cost; first on ties
+
+    def nodes(x, rank0):
+        out = np.empty((m4, n4, 2, H), order="F")
+        out[:, :, :, 0] = rank0(x[:, :, :, 0].reshape(m4, 4, n4, 4, 2), axis=(1, 3))
+        xb = x.reshape(m4, 4, n4, 4, 2, H).transpose(0, 2, 3, 1, 4, 5).reshape(m4, n4, 16, 2, H)
+        # a block that misses rank k altogether takes its first pixel: NaN flow, curvature 0
+        out[:, :, :, 1:] = np.take_along_axis(xb, first[:, :, None, None, :], axis=2)[:, :, 0, :, 1:]
+        return out
+
+    return nodes(flow, np.mean) if curv is None else (nodes(flow, np.mean), nodes(curv, np.sum))

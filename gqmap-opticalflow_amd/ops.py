@@ -127,40 +127,21 @@ def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, d
     lib = _lib.load()
     if subpixel and hypotheses is None:
         hypotheses = 1
+    name, ranks, rank_args = "gqmap_block_match", (), ()
     if hypotheses is not None:
         H = int(hypotheses)
         if not 1 <= H <= 4:  # the shapes below depend on it; the library checks the rest
             raise ValueError(f"block_match: hypotheses must be in 1..4, got {hypotheses}")
-        flow = np.zeros((M, N, 2, H), order="F")
-        cost = np.zeros((M, N, H), order="F")
-        args = (dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), H, int(sep), dptr(flow), dptr(cost))
-        if subpixel:
-            curv = np.zeros((M, N, 2, H), order="F")
-            if host:
-                check(lib.gqmap_block_match_refine_host(*args, dptr(curv)), "gqmap_block_match_refine_host")
-                return (flow, cost, curv, float("nan")) if timed else (flow, cost, curv)
-            ms = C.c_double(0)
-            check(lib.gqmap_block_match_refine(*args, dptr(curv), C.cast(C.byref(ms), _lib._D) if timed else None,
-                                               device), "gqmap_block_match_refine")
-            return (flow, cost, curv, ms.value) if timed else (flow, cost, curv)
-        if host:
-            check(lib.gqmap_block_match_multi_host(*args), "gqmap_block_match_multi_host")
-            return (flow, cost, float("nan")) if timed else (flow, cost)
-        ms = C.c_double(0)
-        check(lib.gqmap_block_match_multi(*args, C.cast(C.byref(ms), _lib._D) if timed else None, device),
-              "gqmap_block_match_multi")
-        return (flow, cost, ms.value) if timed else (flow, cost)
-    flow = np.zeros((M, N, 2), order="F")
-    cost = np.zeros((M, N), order="F")
-    if host:
-        check(lib.gqmap_block_match_host(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), dptr(flow),
-                                         dptr(cost)), "gqmap_block_match_host")
-        return (flow, cost, float("nan")) if timed else (flow, cost)
-    ms = C.c_double(0)
-    check(lib.gqmap_block_match(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), dptr(flow),
-                                dptr(cost), C.cast(C.byref(ms), _lib._D) if timed else None, device),
-          "gqmap_block_match")
-    return (flow, cost, ms.value) if timed else (flow, cost)
+        name, ranks, rank_args = name + ("_refine" if subpixel else "_multi"), (H,), (H, int(sep))
+    out = [np.zeros((M, N, 2) + ranks, order="F"), np.zeros((M, N) + ranks, order="F")]  # flow, cost
+    if subpixel:
+        out.append(np.zeros((M, N, 2) + ranks, order="F"))  # curv
+    ms = C.c_double(float("nan"))
+    tail = () if host else (C.cast(C.byref(ms), _lib._D) if timed else None, device)
+    name += "_host" if host else ""
+    check(getattr(lib, name)(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), *rank_args,
+                             *map(dptr, out), *tail), name)
+    return (*out, ms.value) if timed else tuple(out)
 
 
 def structure_texture(im, theta: float = 0.125, n_iter: int = 100, alp: float = 0.95, device: int = 0,

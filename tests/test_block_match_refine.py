@@ -75,6 +75,17 @@ def test_cost_and_picks_are_those_of_the_integer_matcher(crop, params):
         assert np.any(d != 0) and np.any(curv > 0)
 
 
+def test_the_modes_agree_with_each_other():
+    """What tests/test_gpu_block_match.py asks of the device at the same crop
+    and parameters, here of the host model it is compared with."""
+    from gqmap_opticalflow_amd import block_match
+    crop, par = R.CROPS[3], (7, 7, 3, 1.7)
+    flow, cost = block_match(*R.crop_pair(crop), *par, host=True)
+    for ranked in (multi(crop, par, 1), multi(crop, par, 3)):
+        assert np.array_equal(bits(flow), bits(ranked[0][..., 0])) and np.array_equal(bits(cost), bits(ranked[1][..., 0]))
+    assert np.array_equal(bits(model(crop, par, 3)[1]), bits(multi(crop, par, 3)[1]))
+
+
 def test_one_hypothesis_is_the_default_of_subpixel():
     from gqmap_opticalflow_amd import block_match
     A, B = R.crop_pair(R.CROPS[3])

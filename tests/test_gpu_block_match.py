@@ -8,26 +8,9 @@ import numpy as np
 import pytest
 
 from tests import _blockmatch_np as R
+from tests._blockmatch_gpu import assert_bit_equal, bits, both, force_cols
 
 pytestmark = pytest.mark.gpu
-
-
-def both(A, B, params):
-    from gqmap_opticalflow_amd import block_match
-    return block_match(A, B, *params), block_match(A, B, *params, host=True)
-
-
-def assert_bit_equal(dev, host):
-    for d, h, what in zip(dev, host, ("flow", "cost")):
-        assert d.shape == h.shape
-        assert np.array_equal(d.view(np.uint64), h.view(np.uint64)), what
-
-
-def force_cols(cols):
-    from gqmap_opticalflow_amd import _lib
-    f = _lib.load().gqmap_debug_block_match_cols
-    f.restype, f.argtypes = C.c_int, [C.c_int]
-    assert f(cols) == 0
 
 
 @pytest.mark.parametrize("params", R.PARAMS, ids=str)
@@ -55,6 +38,29 @@ def test_several_tiles_with_partial_tiles_at_every_tile_width(cols):
         assert_bit_equal(*both(A, B, (7, 7, 3, 1.7)))
         if cols == 32:
             assert_bit_equal(*both(*R.crop_pair(R.CROPS[0]), (32, 32, 4, 2.0)))
+    finally:
+        force_cols(0)
+
+
+@pytest.mark.parametrize("cols", [8, 16, 32])
+def test_the_modes_agree_with_each_other_on_the_device(cols):
+    """The three modes are one kernel template, so what a change to it could
+    break silently is their agreement.  33 x 17: two tile rows, the second with
+    one live row, and a partial tile column at every width.  The host model
+    satisfies the same identities (tests/test_block_match_refine.py)."""
+    from gqmap_opticalflow_amd import block_match
+    A, B = R.crop_pair(R.CROPS[3])
+    par = (7, 7, 3, 1.7)
+    try:
+        force_cols(cols)
+        single = block_match(A, B, *par)
+        one = block_match(A, B, *par, hypotheses=1)
+        mflow, mcost = block_match(A, B, *par, hypotheses=3, sep=2)
+        _, rcost, _ = block_match(A, B, *par, hypotheses=3, sep=2, subpixel=True)
+        assert_bit_equal(single, (one[0][..., 0], one[1][..., 0]))
+        assert_bit_equal(single, (mflow[..., 0], mcost[..., 0]))
+        assert np.array_equal(bits(rcost), bits(mcost))
+        assert_bit_equal(*both(A, B, par, hypotheses=1, subpixel=True))
     finally:
         force_cols(0)
 

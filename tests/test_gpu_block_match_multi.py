@@ -9,32 +9,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import _blockmatch_gpu as BG
 from tests import _blockmatch_np as R
-from tests import _golden as G
-from tests._initflow import make_flow
+from tests._blockmatch_gpu import KEYS, as_fp32, assert_bit_equal, assert_state_equal, flows, force_cols, problem
 
 pytestmark = pytest.mark.gpu
 
-KEYS = G.STATE_KEYS
-
 
 def both(A, B, params, H, sep):
-    from gqmap_opticalflow_amd import block_match
-    return (block_match(A, B, *params, hypotheses=H, sep=sep),
-            block_match(A, B, *params, host=True, hypotheses=H, sep=sep))
-
-
-def assert_bit_equal(dev, host):
-    for d, h, what in zip(dev, host, ("flow", "cost")):
-        assert d.shape == h.shape
-        assert np.array_equal(d.view(np.uint64), h.view(np.uint64)), what
-
-
-def force_cols(cols):
-    from gqmap_opticalflow_amd import _lib
-    f = _lib.load().gqmap_debug_block_match_cols
-    f.restype, f.argtypes = C.c_int, [C.c_int]
-    assert f(cols) == 0
+    return BG.both(A, B, params, hypotheses=H, sep=sep)
 
 
 @pytest.mark.parametrize("params", R.PARAMS, ids=str)
@@ -86,39 +69,6 @@ def test_missing_ranks_and_elapsed_ms():
 
 
 # ---- gqmap_init_state_flows ---------------------------------------------------
-
-def problem(engine):
-    """Golden frames and options (tests/test_gpu_init_flow.py), L = 3: the
-    mixture cases on a 24 x 20 corner, the super case on a 32 x 32 corner
-    (node grid 8 x 8).  The golden ranges (about [-1.6, 1.4]) are
-    narrower than make_flow's [-4, 4], so clamping happens."""
-    d = G.load("super_L3")
-    if engine == "super":
-        I1, I2 = (np.asfortranarray(d[k][:32, :32]) for k in ("I1", "I2"))
-        return I1, I2, dict(d["opts"], L=3), (8, 8)
-    o = dict(G.load("mixture_L3_T")["opts"], L=3)
-    I1, I2 = (np.asfortranarray(d[k][:24, :20]) for k in ("I1", "I2"))
-    return I1, I2, o, (24, 20)
-
-
-def flows(M, N, H, seed):
-    f = np.asfortranarray(np.stack([make_flow(M, N, seed=seed + h) for h in range(H)], axis=3))
-    if H > 1:
-        f[5, 4, :, 1] = np.nan  # a missing rank
-    return f
-
-
-def as_fp32(st):
-    for k in KEYS[:6]:
-        setattr(st, k, np.asfortranarray(getattr(st, k).astype(np.float32).astype(np.float64)))
-    return st
-
-
-def assert_state_equal(a, b, what=""):
-    for k in KEYS:
-        np.testing.assert_array_equal(getattr(a, k), getattr(b, k), err_msg=f"{what} {k}")
-    assert a.it == b.it and a.T == b.T
-
 
 @pytest.mark.parametrize("engine,precision,H", [("mixture", "fp64", 3), ("mixture", "fp64", 2), ("mixture", "fp32", 3),
                                                 ("super", "fp64", 3)])

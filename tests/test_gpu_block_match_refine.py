@@ -9,30 +9,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import _blockmatch_gpu as BG
 from tests import _blockmatch_np as R
-from tests.test_gpu_block_match_multi import as_fp32, assert_state_equal, flows, force_cols, problem
+from tests._blockmatch_gpu import (KEYS, NAN_BITS, as_fp32, assert_bit_equal, assert_state_equal, bits, flows, force_cols,
+                                   problem)
 
 pytestmark = pytest.mark.gpu
 
-NAN_BITS = 0x7FF8000000000000
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
 
 def both(A, B, params, H, sep):
-    from gqmap_opticalflow_amd import block_match
-    return (block_match(A, B, *params, hypotheses=H, sep=sep, subpixel=True),
-            block_match(A, B, *params, host=True, hypotheses=H, sep=sep, subpixel=True))
-
-
-def assert_bit_equal(dev, host):
+    dev, host = BG.both(A, B, params, hypotheses=H, sep=sep, subpixel=True)
     assert len(dev) == len(host) == 3
-    for d, h, what in zip(dev, host, ("flow", "cost", "curv")):
-        assert d.shape == h.shape
-        diff = bits(d) != bits(h)
-        assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} entries differ"
+    return dev, host
 
 
 @pytest.mark.parametrize("params", R.PARAMS, ids=str)
@@ -180,7 +168,6 @@ def test_three_iterations_equal_the_set_state_path():
 
 def test_two_tiles_take_their_columns_of_the_full_widths():
     from gqmap_opticalflow_amd import Engine, initial_state, tile_group_run
-    from tests import _golden as G
     I1, I2, o, (M, N) = problem("mixture")
     f, s = flows(M, N, 3, seed=9), widths(M, N, 3, 10, o)
     want = initial_state(o, M, N, seed=4, flow=f, sigma=s)
@@ -190,7 +177,7 @@ def test_two_tiles_take_their_columns_of_the_full_widths():
         for t in tiles:
             t.init_state_from_flow(f, seed=4, sigma=s)
             got = t.get_state()
-            for k in G.STATE_KEYS[:6]:
+            for k in KEYS[:6]:
                 np.testing.assert_array_equal(getattr(got, k)[:, t.col0:t.col1], getattr(want, k)[:, t.col0:t.col1],
                                               err_msg=f"tile {t.tile} {k}")
             cols += t.col1 - t.col0
@@ -205,7 +192,7 @@ def test_two_tiles_take_their_columns_of_the_full_widths():
         np.testing.assert_array_equal(ttr, tr)
         for t in tiles:
             got = t.get_state()
-            for k in G.STATE_KEYS[:6]:
+            for k in KEYS[:6]:
                 np.testing.assert_array_equal(getattr(got, k)[:, t.col0:t.col1], getattr(ref, k)[:, t.col0:t.col1],
                                               err_msg=f"tile {t.tile} {k} after 3 iterations")
     finally:
