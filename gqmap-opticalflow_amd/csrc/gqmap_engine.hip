@@ -4800,6 +4800,16 @@ int gqmap_debug_flow(gqmap_ctx *c)
     return launch_flow(c, 1, true) ? 1 : 0;
 }
 
+// Not in the public header (tests): 1 when the context's runs take the
+// persistent launch (k_iter_persist) -- the occupancy query and the snapshot
+// buffers included, as gqmap_debug_flow does for the dataflow launch.
+int gqmap_debug_persist(gqmap_ctx *c)
+{
+    if (!c || !c->have_images) return 0;
+    DeviceGuard dg(c->device);
+    return launch_persist(c, 1, true) ? 1 : 0;
+}
+
 // Not in the public header (tests, scripts): the iterations a dataflow
 // context runs per launch (FLOW_CHUNK).
 int gqmap_debug_flow_chunk(void) { return FLOW_CHUNK; }

@@ -310,6 +310,15 @@ class Engine:
         f.argtypes = [C.c_void_p]
         return bool(f(self.ctx))
 
+    def persistent(self) -> bool:
+        """Whether runs take the persistent launch (k_iter_persist, a chunk of
+        iterations per launch behind a grid barrier: the small ctf levels;
+        gqmap_debug_persist).  It is tried before the dataflow launch."""
+        f = self.lib.gqmap_debug_persist
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+        return bool(f(self.ctx))
+
     def synchronize(self) -> None:
         check(self.lib.gqmap_synchronize(self.ctx), "gqmap_synchronize")
 
