@@ -147,6 +147,13 @@ struct RootStaged<float> {
 #define GQ_UNROLL_FULL _Pragma("unroll")
 #define GQ_UMUL24(a, b) __umul24((uint32_t)(a), (uint32_t)(b))
 #define GQ_FRACT(x) __builtin_amdgcn_fract(x)  // v_fract_f64
+// the tap table of the offset store (gqmap_math.h vvo2_t) lives in LDS: a
+// pointer in the local address space, so a tap is a ds_read_b64 at base + offset
+#define GQ_LDS_AS __attribute__((address_space(3)))
+#define GQ_LUT_AT(lut, o) (*(const GQ_LDS_AS double *)((const GQ_LDS_AS char *)(lut) + (o)))
+#define GQ_SCHED_FENCE __builtin_amdgcn_sched_barrier(0)
+#define GQ_PIN64(x) asm volatile("" : "+v"(x))
+#define GQ_PIN_UNIFORM(x) asm volatile("" : "+s"(x))
 #include "gqmap_math.h"
 
 namespace gq {
@@ -957,6 +964,19 @@ __device__ __forceinline__ void tile_totals_tail(const FinParams &F, int total, 
     if (tid == 0) ctl->arrive = 0;
 }
 
+// Where a tile's node phase reads its taps: the padded frame, and for the
+// offset store (vvo2_t) the LDS table its taps index.
+template <typename R, typename VT>
+__device__ __forceinline__ auto tile_frame_view(const IterParams<R, VT> &P, const GQ_LDS_AS double *taplut)
+{
+    if constexpr (is_vvo2<VT>::value) {
+        return frame_view_lut(P.VV, P.M2, taplut);
+    } else {
+        (void)taplut;
+        return frame_view(P.VV, P.M2);
+    }
+}
+
 // One tile of one iteration (absolute iteration `it`, reading state buffer
 // `parity`): node and edge gradients, neighbour scatter, clamped ascent into
 // the other buffer, and the tile's exact partial sums into partial row part_r.
@@ -980,7 +1000,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
                                           int part_r, TileLdsQ<R, Q> &lds, int l0, int l1, double Tcur,
                                           bool tab_ready, unsigned long long *acc_ring = nullptr,
                                           int grows = 0, bool grouped = false, HaloChain<R> *hc = nullptr,
-                                          unsigned halo_tok = 0
+                                          unsigned halo_tok = 0, const GQ_LDS_AS double *taplut = nullptr
 #if GQ_FLOW_TL
                                           , unsigned long long *tlw = nullptr
 #endif
@@ -1099,7 +1119,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         const bool fast = ENG == 0 && __all(!inner || node_unclamped(c, mu_u, mu_v, m, n + P.n_off, P.Mo, P.No,
                                                                      P.gh_xmax, R(ENG == 2 ? CTF_MARGIN : 0.0)));
         if (inner) {
-            const auto fv = frame_view(P.VV, P.M2);
+            const auto fv = tile_frame_view(P, taplut);
             // (at one lane per node only with float taps: the fp64-tap Q = 1
             // kernels would cross 168 VGPRs, 3 -> 2 waves per SIMD)
             constexpr bool PF = QA >= GQ_NODE_PF_MIN_Q && (QA > 1 || sizeof(VT) == 4);
@@ -2077,13 +2097,14 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     // form of the node loop (node_sums ROT): the fp64 mixture item on the
     // binary16 pair store at its own register allocation (C2's kernel; not
     // the 3-wave large-frame form, not the float store: not measured)
-    constexpr int ROTF = ENG == 0 && Q == 1 && !LIT && W == 0 && sizeof(R) == 8 && is_vvh2<VT>::value
-                             ? (GQ_NODE_ROT_FLOW_FP64 | NODE_UNROLL(GQ_NODE_UNROLL_FLOW_FP64))
+    // (the offset store's loop, node_sums_lut, takes the trips per pass only)
+    constexpr int ROTF = ENG == 0 && Q == 1 && !LIT && W == 0 && sizeof(R) == 8 && is_vvpair<VT>::value
+                             ? ((is_vvo2<VT>::value ? 0 : GQ_NODE_ROT_FLOW_FP64) | NODE_UNROLL(GQ_NODE_UNROLL_FLOW_FP64))
                              : GQ_NODE_ROT_OTHER;
     // the halo job of the plain items (iter_tile HALO): the same fp64 item,
     // and the fp64 ctf levels under their own switch
     constexpr int HALO = !GRP || LIT || W != 0 || sizeof(R) != 8 ? 0
-                         : ENG == 0 && is_vvh2<VT>::value ? GQ_FLOW_HALO
+                         : ENG == 0 && is_vvpair<VT>::value ? GQ_FLOW_HALO
                          : ENG == 2 ? GQ_FLOW_HALO_CTF : 0;
     HaloChain<R> *hc = nullptr;
     if constexpr (HALO == 1) {
@@ -2092,6 +2113,17 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
         // (tokens start at 1; the claim's barrier below orders this before the first item)
         if (threadIdx.x < 4) sh_halo.flag[threadIdx.x] = 0;
         if (threadIdx.x == 0) sh_halo.fail = bar + BAR_FAIL;
+    }
+    // the offset store (vvo2_t): the tap table vmin .. vmin + vn - 1 as doubles,
+    // filled once per launch from the two words behind the store's elements
+    // (the claim's barrier below orders it before the first item)
+    const GQ_LDS_AS double *taplut = nullptr;
+    if constexpr (is_vvo2<VT>::value) {
+        __shared__ double sh_taplut[TAPLUT_N];
+        const int *hdr = reinterpret_cast<const int *>(P.VV + vv_elems(P.Mo, P.No));
+        const int vmin = hdr[0], vn = min(hdr[1], TAPLUT_N);
+        for (int e = threadIdx.x; e < vn; e += BLOCK) sh_taplut[e] = taplut_entry(e, vmin);
+        taplut = (const GQ_LDS_AS double *)sh_taplut;
     }
     const int vr = P.M - (P.tiles_m - 1) * tile_rows(Q);
     const bool groups = GRP && GQ_FLOW_ROWS && vr <= 4;
@@ -2178,10 +2210,10 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
         // (the halo chain's token: this workgroup's claims only grow)
         if (MIX && edge_first)
             iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
-                                                                                wrows, grouped, hc, (unsigned)i + 1 GQ_TLW_ARG);
+                                                                                wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
         else
             iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
-                                                                                 wrows, grouped, hc, (unsigned)i + 1 GQ_TLW_ARG);
+                                                                                 wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
 #undef GQ_TLW_ARG
         // publish: every wave's stores (state, rou, the slot's sums) are done
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2580,6 +2612,7 @@ struct Policy {
     int flow = -1;         // dataflow launch (k_iter_flow): -1 auto (fp64 whole grids at Q = 1, 2), 0 off, 1 on
     int vv_float = 1;      // float padded-frame store when exact
     int vv_pair = 1;       // binary16 column-pair store when exact (fp64 single-scale mixture, Q = 1)
+    int tap_lut = 1;       // offset store beside it, taps by LDS table (fp64 dataflow item; GQ_TAP_LUT)
     int verbose = 0;       // recovery messages on stderr
 };
 Policy g_pol;
@@ -2620,6 +2653,11 @@ struct gqmap_ctx {
     bool have_images = false, have_state = false;
     bool vv32 = false;  // VV stored as float (exact: integer-valued frames)
     bool vvp = false;   // VV stored as binary16 column pairs (vvh2_t; gqmap_math.h, policy vv_pair)
+    // vvp, fp64: the frame also as table offsets (vvo2_t; gqmap_math.h, policy
+    // tap_lut) in d_VO, vv_elems elements and two words (vmin, table entries);
+    // read by the dataflow launch only -- every other reader takes d_VV
+    bool tapt = false;
+    void *d_VO = nullptr;
     bool lit = false;   // GQMAP_ARITH_LITERAL: k_iter_lit, literal table layout
     int split = 1;      // lanes per node of the arithmetic (Q): 1, 2, 4, 8, 16, 64
     int kq = 1;         // kernel shape: split, or 0 = role split (Q = 1 arithmetic, 16 x 8 tiles)
@@ -2840,7 +2878,7 @@ IterParams<R, VT> iter_params(const gqmap_ctx *c)
 {
     IterParams<R, VT> P;
     const gqmap_options &o = c->opt;
-    P.VV = (const VT *)c->d_VV;
+    P.VV = (const VT *)(is_vvo2<VT>::value ? c->d_VO : c->d_VV);
     P.I1 = (const R *)c->d_I1;
     P.st0 = (R *)c->d_st[0];
     P.st1 = (R *)c->d_st[1];
@@ -3685,7 +3723,7 @@ bool launch_flow_q(gqmap_ctx *c, int n, bool dry)
                                                        (const R *)c->d_st[1], (R *)c->d_snap, c->d_snap_ctl, nv);
     }
     IterParams<R, VT> P = iter_params<R, VT>(c);
-    if constexpr (ENG == 0 && Q == 1 && !LIT) {
+    if constexpr (ENG == 0 && Q == 1 && !LIT && !is_vvo2<VT>::value) {  // (launch_flow: no offset store there)
         // a large frame (C5: ~14k tiles) has slack enough at any occupancy and
         // wants the latency hiding of 3 waves per SIMD: 2 waves measured
         // 2551 -> 2726 us per iteration on C5
@@ -3755,6 +3793,12 @@ bool launch_flow(gqmap_ctx *c, int n, bool dry)
     if (c->fp32)
         return c->vvp ? !c->lit && c->kq == 1 && launch_flow_q<float, vvh2_t, 0, 1>(c, n, dry)
                       : launch_flow_t<float, float>(c, n, dry);
+#if GQ_TAP_LUT
+    // taps by LDS table (the offset store, gqmap_set_images); not the
+    // 3-wave form of the large frames, which keeps the pair store's kernel
+    if (c->vvp && c->tapt && c->tiles_m * c->tiles_n <= GQ_FLOW_WIDE_ITEMS)
+        return !c->lit && c->kq == 1 && launch_flow_q<double, vvo2_t, 0, 1>(c, n, dry);
+#endif
     if (c->vvp) return !c->lit && c->kq == 1 && launch_flow_q<double, vvh2_t, 0, 1>(c, n, dry);
     if (c->vv32) return launch_flow_t<double, vvs_t>(c, n, dry);
     return launch_flow_t<double, double>(c, n, dry);
@@ -3995,6 +4039,9 @@ gqmap_status prepare_images(gqmap_ctx *c, int Mo, int No, bool vv32, bool vvp = 
         if (c->d_VV) (void)hipFree(c->d_VV);
         if (c->d_I1) (void)hipFree(c->d_I1);
         c->d_VV = c->d_I1 = nullptr;
+        if (c->d_VO) (void)hipFree(c->d_VO);  // (gqmap_set_images makes the offset store anew)
+        c->d_VO = nullptr;
+        c->tapt = false;
         // a truth belongs to the previous grid (k_iter indexes it with M, N)
         if (c->d_truth) (void)hipFree(c->d_truth);
         c->d_truth = nullptr;
@@ -4296,6 +4343,46 @@ gqmap_status gqmap_set_images(gqmap_ctx *c, const double *I1, const double *I2, 
             }
         GQ_HIP(hipMemcpyAsync(c->d_VV, vp.data(), vp.size() * sizeof(vvh2_t), hipMemcpyHostToDevice, c->stream));
         GQ_HIP(hipStreamSynchronize(c->stream));
+        // fp64: the offset store beside it (gqmap_math.h vvo2_t) when every
+        // value is an integer and they span, with the 0 of the zero column and
+        // the buffer's tail, at most a table's worth.  The pair store stays:
+        // the per-launch kernels (the recovery path), gqmap_log_p and the
+        // read-back take it.
+        bool tapt = GQ_TAP_LUT && c->pol.tap_lut && !c->fp32;
+        int vmin = 0, vmax = 0;
+        for (size_t k = 0; tapt && k < VV.size(); ++k) {
+            const int vi = (int)VV[k];  // (|v| <= 65504: exact in binary16)
+            if ((double)vi != VV[k]) tapt = false;
+            vmin = std::min(vmin, vi);
+            vmax = std::max(vmax, vi);
+        }
+        if (tapt && vmax - vmin + 1 > TAPLUT_N) tapt = false;
+        if (tapt != c->tapt) drop_graph(c);  // (the captured launches name the kernel of the other store)
+        c->tapt = false;  // (until the store is there)
+        if (tapt) {
+            // (an upload that fails leaves no captured launch of the offset store's kernel behind)
+            struct Undo {
+                gqmap_ctx *c;
+                bool armed;
+                ~Undo() { if (armed) drop_graph(c); }
+            } undo{c, true};
+            const size_t ne = vv_elems(Mo, No);
+            if (!c->d_VO) GQ_HIP(hipMalloc(&c->d_VO, ne * sizeof(vvo2_t) + 2 * sizeof(int)));
+            const uint16_t zero = taplut_offset(0, vmin);
+            std::vector<vvo2_t> vo(ne + 2, vvo2_t{zero, zero});
+            for (size_t cc = 0; cc < N2; ++cc)
+                for (size_t r = 0; r < M2; ++r) {
+                    vo[r + M2 * cc].lo = taplut_offset((int)VV[r + M2 * cc], vmin);
+                    if (cc + 1 < N2) vo[r + M2 * cc].hi = taplut_offset((int)VV[r + M2 * (cc + 1)], vmin);
+                }
+            const int hdr[2] = {vmin, vmax - vmin + 1};
+            static_assert(sizeof(hdr) == 2 * sizeof(vvo2_t), "the two words behind the elements");
+            std::memcpy(&vo[ne], hdr, sizeof(hdr));
+            GQ_HIP(hipMemcpyAsync(c->d_VO, vo.data(), vo.size() * sizeof(vvo2_t), hipMemcpyHostToDevice, c->stream));
+            GQ_HIP(hipStreamSynchronize(c->stream));
+            c->tapt = true;
+            undo.armed = false;
+        }
     } else if (vv32 && !c->fp32) {
         std::vector<vvs_t> vc(VV.size());
         for (size_t k = 0; k < VV.size(); ++k) vc[k] = (vvs_t)VV[k];
@@ -4829,6 +4916,7 @@ int gqmap_debug_policy(const char *name, int value)
         {"persist", &g_pol.persist, 1},      {"persist_cap", &g_pol.persist_cap, -1},
         {"graph", &g_pol.graph, 1},          {"vv_float", &g_pol.vv_float, 1}, {"vv_pair", &g_pol.vv_pair, 1},
         {"verbose", &g_pol.verbose, 0},      {"flow", &g_pol.flow, -1},
+        {"tap_lut", &g_pol.tap_lut, 1},
     };
     for (const Field &f : fields)
         if (std::strcmp(f.n, name) == 0) {
@@ -4989,6 +5077,53 @@ gqmap_status gqmap_debug_read_vv(gqmap_ctx *c, double *out, size_t n, int *store
         else out[k] = (double)((const vvs_t *)raw.data())[k];
     }
     return GQMAP_OK;
+}
+
+// Not in the public header (tests): 1 when the context's dataflow launches
+// read the offset store (taps by LDS table), 0 when they read the pair store.
+int gqmap_debug_tap_lut(const gqmap_ctx *c) { return c && c->have_images && c->vvp && c->tapt ? 1 : 0; }
+
+// Not in the public header (tests): the offset store decoded through its
+// table -- lo[k], hi[k] the values of the two halves of element k of the
+// (Mo+2) x (No+2) frame, *tail the number of elements behind it (the zero
+// column and the tail) that do not decode to 0, range[0..1] = vmin and the
+// table's entries.
+gqmap_status gqmap_debug_read_vo(gqmap_ctx *c, double *lo, double *hi, size_t n, int *tail, int range[2])
+{
+    clear_error();
+    GQ_CHECK(c && lo && hi && tail && range, GQMAP_ERR_INVALID_ARG, "null argument");
+    GQ_CHECK(c->have_images && c->vvp && c->tapt && c->d_VO, GQMAP_ERR_STATE, "no offset store");
+    const size_t nvv = (size_t)(c->Mo + 2) * (c->No + 2), ne = vv_elems(c->Mo, c->No);
+    GQ_CHECK(n >= nvv, GQMAP_ERR_INVALID_ARG, "buffer holds %zu of %zu values", n, nvv);
+    DeviceGuard dg(c->device);
+    std::vector<vvo2_t> raw(ne + 2);
+    GQ_HIP(hipMemcpyAsync(raw.data(), c->d_VO, raw.size() * sizeof(vvo2_t), hipMemcpyDeviceToHost, c->stream));
+    GQ_HIP(hipStreamSynchronize(c->stream));
+    std::memcpy(range, &raw[ne], 2 * sizeof(int));
+    auto value = [&](uint16_t o) { return o % 8 == 0 && o / 8 < range[1] ? taplut_entry(o / 8, range[0]) : (double)NAN; };
+    for (size_t k = 0; k < nvv; ++k) {
+        lo[k] = value(raw[k].lo);
+        hi[k] = value(raw[k].hi);
+    }
+    *tail = 0;
+    for (size_t k = nvv; k < ne; ++k) *tail += (value(raw[k].lo) != 0.0) + (value(raw[k].hi) != 0.0);
+    return GQMAP_OK;
+}
+
+// Not in the public header (tests): resident workgroups per CU of the
+// dataflow kernel an fp64 context on the pair store runs at its frame size
+// (launch_flow's choice; the occupancy query its launches size their grid by);
+// -1 for any other context.
+int gqmap_debug_flow_per_cu(gqmap_ctx *c)
+{
+    if (!c || !c->have_images || !c->vvp || c->fp32) return -1;
+    DeviceGuard dg(c->device);
+    // (above GQ_FLOW_WIDE_ITEMS the 3-wave form of the pair store's kernel, whatever the store)
+    if (c->tiles_m * c->tiles_n > GQ_FLOW_WIDE_ITEMS) return kernel_shape(k_iter_flow<double, vvh2_t, 0, 1, false, 3>).x;
+#if GQ_TAP_LUT
+    if (c->tapt) return kernel_shape(k_iter_flow<double, vvo2_t, 0, 1, false, 0>).x;
+#endif
+    return kernel_shape(k_iter_flow<double, vvh2_t, 0, 1, false, 0>).x;
 }
 
 gqmap_status gqmap_synchronize(gqmap_ctx *c)
@@ -5319,7 +5454,7 @@ void gqmap_destroy(gqmap_ctx *c)
     if (c->own_gathered && c->d_gathered) (void)hipFree(c->d_gathered);
     for (void *p : c->d_halo)
         if (p) (void)hipFree(p);
-    void *bufs[] = {c->d_VV, c->d_I1, c->d_st[0], c->d_st[1], c->d_tab, c->d_ctl, (void *)c->d_partials, c->d_trace,
+    void *bufs[] = {c->d_VV, c->d_VO, c->d_I1, c->d_st[0], c->d_st[1], c->d_tab, c->d_ctl, (void *)c->d_partials, c->d_trace,
                     c->d_truth, (void *)c->d_bar, c->d_snap, (void *)c->d_snap_ctl, (void *)c->d_flow};
     for (void *p : bufs)
         if (p) (void)hipFree(p);

@@ -218,6 +218,38 @@ struct is_vvh2 : std::is_same<typename std::remove_cv<T>::type, vvh2_t> {};
 template <typename T>
 struct is_vvh2 : std::false_type {};
 #endif
+// Offset storage of the padded frame (policy tap_lut; beside the pair store,
+// for the fp64 mixture item of the dataflow launch): the same column-pair
+// layout, each half the byte offset 8 (value - vmin) of the tap's double in a
+// table of the integers vmin .. vmin + n - 1 that the kernel keeps in LDS, so
+// a tap is one 16-bit extraction and one 8-byte table read where the pair
+// store takes two conversions (binary16 -> float -> double).  For integer
+// frames whose padded values, and the 0 of the buffer's tail, span at most
+// TAPLUT_N integers: every such value is exact in binary16 (|v| <= 2048), so
+// the table entry (double)(vmin + i) is the double the conversions give --
+// the same operands into the same fma chains.
+constexpr int TAPLUT_N = 1276;  // the padded values of an 8-bit frame lie in [-510, 765]
+struct alignas(4) vvo2_t {
+    uint16_t lo, hi;  // columns c, c + 1
+};
+template <typename T>
+struct is_vvo2 : std::is_same<typename std::remove_cv<T>::type, vvo2_t> {};
+template <typename T>
+struct is_vvpair : std::integral_constant<bool, is_vvh2<T>::value || is_vvo2<T>::value> {};
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+constexpr uint16_t taplut_offset(int value, int vmin) { return (uint16_t)((value - vmin) * 8); }
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+constexpr double taplut_entry(int i, int vmin) { return (double)(vmin + i); }
+// The table entry at byte offset o of table `lut` (an includer may keep the
+// table in another address space and define its own form).
+#ifndef GQ_LUT_AT
+#define GQ_LUT_AT(lut, o) (*(const double *)((const char *)(lut) + (o)))
+#endif
+
 template <typename R, typename E>
 GQ_HD R tap_col(const E &e, int half)
 {
@@ -288,7 +320,7 @@ GQ_HD auto load_taps16(VP VV, uint32_t o, uint32_t M2)
     constexpr uint32_t EB = (uint32_t)sizeof(E);
     const uint32_t ob = o * EB, cb = M2 * EB;
     Taps16<E> T;
-    if constexpr (is_vvh2<E>::value) {  // v[4 p + r]: row r of column pair p (columns 2p, 2p + 1)
+    if constexpr (is_vvpair<E>::value) {  // v[4 p + r]: row r of column pair p (columns 2p, 2p + 1)
         for (int pr = 0; pr < 2; ++pr) {
             const auto col = byte_ptr(VV, ob + (uint32_t)(2 * pr) * cb);
             for (int r = 0; r < 4; ++r) T.v[4 * pr + r] = col[r];
@@ -378,6 +410,36 @@ template <typename VP>
 GQ_HD TapView<VP> frame_view(VP VV, int M2)
 {
     return TapView<VP>{VV, (uint32_t)M2};
+}
+// ... of the offset store, with the table its taps index (vvo2_t)
+template <typename VP, typename LP>
+struct TapViewLut {
+    VP p;
+    uint32_t ld;
+    LP lut;
+    GQ_HD uint32_t cell(int iy, int ix) const { return cell_elem(iy, ix, (int)ld); }
+};
+template <typename VP, typename LP>
+GQ_HD TapViewLut<VP, LP> frame_view_lut(VP VV, int M2, LP lut)
+{
+    return TapViewLut<VP, LP>{VV, (uint32_t)M2, lut};
+}
+// The sixteen taps of an offset-store cell as their table entries
+// (GQ_LUT_AT), in the column-major order of the plain stores: the values the
+// pair store's conversions give, so bicubic_taps4 runs its column chains on
+// the same operands.
+// (mask = 0xffff, shift = 16: the halves of an element as one word)
+template <typename LP>
+GQ_HD Taps16<double> lut_taps16(LP lut, const Taps16<vvo2_t> &T, uint32_t mask = 0xffffu, uint32_t shift = 16)
+{
+    Taps16<double> D;
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r) {
+            const vvo2_t &e = T.v[4 * (c >> 1) + r];
+            const uint32_t w = (uint32_t)e.lo | (uint32_t)e.hi << 16;
+            D.v[4 * c + r] = GQ_LUT_AT(lut, (c & 1) ? w >> shift : w & mask);
+        }
+    return D;
 }
 
 // Elements of a padded-frame (VV) buffer: the (Mo+2) x (No+2) frame, then
@@ -936,12 +998,93 @@ GQ_HD NodeCoef<R> node_coef(R o1, R o2, R p)
 constexpr int NODE_ROT = 1, NODE_ROT_STAGE = 2, NODE_ROT_FLAGS = 255;
 constexpr int NODE_UNROLL(int n) { return n << 8; }
 constexpr int node_rot_unroll(int rot) { return (rot >> 8) > 1 ? (rot >> 8) : 1; }
+// The pipelined loop (PF, one lane per node: k0 = 0, dk = 1 in use) of the
+// fp64 single-scale engine on the offset store, V a TapViewLut: the same
+// operations on the same operands in the same order as node_sums' loop on
+// the pair store, a tap's value read from the table.  A trip has three parts,
+// kept apart for the instruction scheduler (GQ_SCHED_FENCE, an includer's
+// scheduling barrier: left alone the compiler sinks each table read to its
+// use and waits for it alone, and the next sample's loads to the top of the
+// next trip): the sixteen table reads of sample k; the position arithmetic
+// and the loads of sample k + dk, the reads in flight behind them; then the
+// interpolation, the root and the sums of sample k.  The barrier holds memory
+// operations only; GQ_PIN64 / GQ_PIN_UNIFORM (a per-lane double, a uniform
+// word) make the arithmetic that needs a value start behind a point of the
+// trip.  UNR trips per pass are written out (a loop holding the barrier is
+// not unrolled by pragma).  Measured forms: profiles/lds_offload_ab.txt.
+#ifndef GQ_SCHED_FENCE  // (a host includer: nothing to schedule)
+#define GQ_SCHED_FENCE (void)0
+#define GQ_PIN64(x) (void)(x)
+#define GQ_PIN_UNIFORM(x) (void)(x)
+#endif
+template <bool CLAMP, int UNR, typename TP, typename TV, typename IP>
+GQ_HD Sums<double> node_sums_lut(TP tab, int k0, int K2, int dk, const TV &V, IP I1, int Mo, int No, double eps,
+                                 const NodeCoef<double> &c, double u1, double u2, int m, int n)
+{
+    Sums<double> S;
+    if (k0 >= K2) return S;
+    const double I = I1[m + (int64_t)Mo * n];
+    const double U1 = u1 + double(n + 1), U2 = u2 + double(m + 1);
+    // cell and fractions of the sample at the table's point (xi, xj)
+    auto locate = [&](double xi, double xj, double &so, double &to) -> uint32_t {
+        const double x1 = fma(c.ax, xi, fma(c.bx, xj, U1));
+        const double x2 = fma(c.ay, xi, fma(c.by, xj, U2));
+        return cell4_abs_v<CLAMP>(V, Mo, No, x1, x2, so, to);
+    };
+    const int klast = k0 + (K2 - 1 - k0) / dk * dk;
+    double so, to;
+    auto T = load_taps16(V.p, locate(tab[tab_at(T_XI, k0)], tab[tab_at(T_XJ, k0)], so, to), V.ld);
+    // the point a trip locates, read from the table a trip ahead (beside the
+    // weights of the sums, so the trip's second part does not wait for it)
+    const int kn0 = k0 + dk <= klast ? k0 + dk : klast;
+    double nxi = tab[tab_at(T_XI, kn0)], nxj = tab[tab_at(T_XJ, kn0)];
+    auto trip = [&](int k) {
+        // (the extraction too stays behind the trip before: its mask and shift from here on)
+        uint32_t mask = 0xffffu, shift = 16;
+        GQ_PIN_UNIFORM(mask);
+        GQ_PIN_UNIFORM(shift);
+        const Taps16<double> D = lut_taps16(V.lut, T, mask, shift);
+        GQ_SCHED_FENCE;
+        double sok = so, tok = to;
+        T = load_taps16(V.p, locate(nxi, nxj, so, to), V.ld);  // sample min(k + dk, klast): the last pass reloads its own cell
+        GQ_SCHED_FENCE;
+        // (the fence orders memory operations only: the arithmetic of the
+        // third part starts from here)
+        GQ_PIN64(sok);
+        GQ_PIN64(tok);
+        const int kn2 = k + 2 * dk <= klast ? k + 2 * dk : klast;
+        nxi = tab[tab_at(T_XI, kn2)];
+        nxj = tab[tab_at(T_XJ, kn2)];
+        const double d = fma(bicubic_taps4<double>(D, sok, tok), -0.25, I);
+        S.add(tab, k, GQ_SQRT(fma(d, d, eps)));
+        // (the sums, and the wait for their weights, before the next trip's
+        // table reads: those then have the position arithmetic to run behind)
+        GQ_PIN64(S.s0); GQ_PIN64(S.sxi); GQ_PIN64(S.sxj);
+        GQ_PIN64(S.sa); GQ_PIN64(S.sm); GQ_PIN64(S.sx);
+        GQ_SCHED_FENCE;
+    };
+    int k = k0;
+    GQ_PAIR_UNROLL_K(1)
+    for (; k + (UNR - 1) * dk <= klast; k += UNR * dk) {
+        GQ_UNROLL_FULL
+        for (int u = 0; u < UNR; ++u) trip(k + u * dk);
+    }
+    if constexpr (UNR > 1) {
+        GQ_PAIR_UNROLL_K(1)
+        for (; k <= klast; k += dk) trip(k);
+    }
+    return S;
+}
 template <int ENG, bool CLAMP = true, bool PF = false, int ROT = 0, typename R, typename TP, typename TV, typename IP>
 GQ_HD Sums<R> node_sums(TP tab, int k0, int K2, int dk, const TV &V, IP I1, int Mo, int No,
                         R eps, const NodeCoef<R> &c, R u1, R u2, int m, int n)
 {
     Sums<R> S;
-    if constexpr (PF && ENG != 1) {
+    if constexpr (is_vvo2<typename std::remove_cv<typename std::remove_reference<decltype(*V.p)>::type>::type>::value) {
+        static_assert(PF && ENG == 0 && sizeof(R) == 8 && (ROT & NODE_ROT_FLAGS) == 0,
+                      "the offset store: the fp64 single-scale engine's pipelined loop, not rotated");
+        return node_sums_lut<CLAMP, node_rot_unroll(ROT)>(tab, k0, K2, dk, V, I1, Mo, No, eps, c, u1, u2, m, n);
+    } else if constexpr (PF && ENG != 1) {
         const R I = I1[m + (int64_t)Mo * n];
         constexpr bool ABS = ENG == 0 && sizeof(R) == 8;
         const R U1 = ABS ? u1 + R(n + 1) : u1, U2 = ABS ? u2 + R(m + 1) : u2;
@@ -1005,8 +1148,7 @@ GQ_HD Sums<R> node_sums(TP tab, int k0, int K2, int dk, const TV &V, IP I1, int 
             }
         }
         return S;
-    }
-    if constexpr (ENG != 1) {
+    } else if constexpr (ENG != 1) {
         const R I = I1[m + (int64_t)Mo * n];
         if constexpr (ENG == 0 && sizeof(R) == 8) {
             // fp64 single-scale: absolute positions X = j + x1 with the pixel

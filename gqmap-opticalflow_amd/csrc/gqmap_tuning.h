@@ -120,6 +120,16 @@
 #ifndef GQ_FLOW_HALO_SLEEP  // the chain: s_sleep between two polls of the hand-over flag
 #define GQ_FLOW_HALO_SLEEP 1
 #endif
+// Tap conversion by LDS table in the fp64 mixture item of the dataflow launch
+// at one lane per node (k_iter_flow<double, vvo2_t, 0, 1>, plain and grouped
+// items; not the 3-wave large-frame form): integer frames within a table's
+// range (gqmap_math.h TAPLUT_N) get an offset store beside the binary16 pair
+// store, and a tap is a 16-bit extraction and a ds_read_b64 in place of two
+// conversions.  0: the kernel is not built and every frame takes the pair
+// store's kernel (run-time: policy tap_lut).
+#ifndef GQ_TAP_LUT
+#define GQ_TAP_LUT 1
+#endif
 #ifndef GQ_UNROLL_MIN_Q
 #define GQ_UNROLL_MIN_Q 2
 #endif
