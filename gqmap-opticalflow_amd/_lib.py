@@ -39,6 +39,7 @@ EXPORTS = (
     "gqmap_structure_texture", "gqmap_structure_texture_host",
     "gqmap_block_match_multi", "gqmap_block_match_multi_host", "gqmap_init_state_flows",
     "gqmap_block_match_refine", "gqmap_block_match_refine_host", "gqmap_init_state_seeded",
+    "gqmap_flow_consistency", "gqmap_flow_consistency_host", "gqmap_flow_fill", "gqmap_flow_fill_host",
 )
 CTF_MAX_LEVELS = 8
 
@@ -167,6 +168,10 @@ def load():
         "gqmap_block_match_refine_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                                     C.c_int, C.c_int, _D, _D, _D]),
         "gqmap_init_state_seeded": (C.c_int, [vp, _D, _D, C.c_int, C.c_uint64]),
+        "gqmap_flow_consistency": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_double, C.c_double, _D, u8, _D, C.c_int]),
+        "gqmap_flow_consistency_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_double, C.c_double, _D, u8]),
+        "gqmap_flow_fill": (C.c_int, [_D, u8, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _D, u8, _D, C.c_int]),
+        "gqmap_flow_fill_host": (C.c_int, [_D, u8, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _D, u8]),
         "gqmap_structure_texture": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _D, _D,
                                               _D, C.c_int]),
         "gqmap_structure_texture_host": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "gqmap_blockmatch.h"
+#include "gqmap_flowcheck.h"
 #include "gqmap_internal.h"
 #include "gqmap_rof.h"
 
@@ -466,6 +467,82 @@ gqmap_status gqmap_structure_texture_host(const double *im, int M, int N, int C,
              "gqmap_structure_texture_host: texture range [%g, %g] is zero or not finite", tlo, thi);
     for (size_t i = 0; i < n_all; ++i) texture[i] = gq::rof_scale_out(t[i], tlo, thi);
     if (structure) std::memcpy(structure, s.data(), sizeof(double) * n_all);
+    return GQMAP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Forward-backward check and fill, host models: the arithmetic of
+// gqmap_flowcheck.h, pixel by pixel, the fill over zero-padded copies of V, S_0
+// and S_1, one plain Jacobi pass at a time.  Bit for bit what
+// gqmap_flow_consistency and gqmap_flow_fill compute.
+// ---------------------------------------------------------------------------
+extern "C" {
+
+gqmap_status gqmap_flow_consistency_host(const double *fwd, const double *bwd, int M, int N, double a1, double a2,
+                                         double *err, unsigned char *mask)
+{
+    gq::clear_error();
+    GQ_CHECK(fwd && bwd && (err || mask), GQMAP_ERR_INVALID_ARG, "gqmap_flow_consistency_host: null argument");
+    const char *bad = gq::fc_bad_check(M, N, a1, a2);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_flow_consistency_host: %s (M=%d N=%d a1=%g a2=%g)", bad, M, N, a1,
+             a2);
+    for (int n = 0; n < N; ++n)
+        for (int m = 0; m < M; ++m) {
+            double e;
+            const bool ok = gq::fc_check(fwd, bwd, m, n, M, N, a1, a2, &e);
+            const size_t o = m + (size_t)M * n;
+            if (err) err[o] = e;
+            if (mask) mask[o] = ok ? 1 : 0;
+        }
+    return GQMAP_OK;
+}
+
+gqmap_status gqmap_flow_fill_host(const double *flow, const unsigned char *mask, int M, int N, int r, double sigma,
+                                  int passes, double *out, unsigned char *filled)
+{
+    gq::clear_error();
+    GQ_CHECK(flow && mask && out, GQMAP_ERR_INVALID_ARG, "gqmap_flow_fill_host: null argument");
+    const char *bad = gq::fc_bad_fill(M, N, r, sigma, passes);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_flow_fill_host: %s (M=%d N=%d r=%d sigma=%g passes=%d)", bad, M, N,
+             r, sigma, passes);
+    const gq::FcFilter f = gq::fc_filter(r, sigma);
+    const size_t MN = (size_t)M * N, PH = (size_t)M + 2 * r, PW = (size_t)N + 2 * r;
+    std::vector<unsigned char> state(MN), next(MN);
+    std::vector<double> cur(flow, flow + 2 * MN), X(3 * PH * PW), T(3 * (size_t)M * PW), Y(3 * MN);
+    for (size_t i = 0; i < MN; ++i) state[i] = mask[i] ? 0 : GQ_FC_UNFILLED;
+    for (int p = 1; p <= passes; ++p) {
+        // X_q(row, col) = X_q of pixel (row - r, col - r), zero outside the frame
+        std::fill(X.begin(), X.end(), 0.0);
+        for (int n = 0; n < N; ++n)
+            for (int m = 0; m < M; ++m) {
+                const size_t o = m + (size_t)M * n, c = m + r + PH * (n + r);
+                const bool valid = state[o] != GQ_FC_UNFILLED;
+                X[c] = valid ? 1.0 : 0.0;
+                X[c + PH * PW] = valid ? cur[o] : 0.0;
+                X[c + 2 * PH * PW] = valid ? cur[o + MN] : 0.0;
+            }
+        for (int q = 0; q < 3; ++q) {
+            const double *Xq = &X[q * PH * PW];
+            double *Tq = &T[q * (size_t)M * PW];
+            for (size_t c = 0; c < PW; ++c)
+                for (int m = 0; m < M; ++m) Tq[m + (size_t)M * c] = gq::fc_rows(&Xq[m + PH * c], r, f);
+            for (int n = 0; n < N; ++n)
+                for (int m = 0; m < M; ++m) Y[q * MN + m + (size_t)M * n] = gq::fc_cols(&Tq[m + (size_t)M * n], M, r, f);
+        }
+        for (size_t o = 0; o < MN; ++o) {
+            const bool fill = gq::fc_fills(state[o], Y[o]);
+            if (fill) {
+                cur[o] = Y[MN + o] / Y[o];
+                cur[o + MN] = Y[2 * MN + o] / Y[o];
+            }
+            next[o] = fill ? (unsigned char)p : state[o];
+        }
+        state.swap(next);
+    }
+    std::memcpy(out, cur.data(), sizeof(double) * 2 * MN);
+    if (filled) std::memcpy(filled, state.data(), MN);
     return GQMAP_OK;
 }
 

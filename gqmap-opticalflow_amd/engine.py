@@ -473,7 +473,9 @@ def gqmap_gpuSuper_mix_entropy(options: dict, I1, I2, **kw):
 def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7,
                      engine: str = "mixture", device: int = 0, host: bool = False,
                      hypotheses: int | None = None, sep: int = 2, subpixel: bool = False,
-                     sigma_from_cost: bool = False, lambdad: float = 1.0, sigma_min: float = 0.5):
+                     sigma_from_cost: bool = False, lambdad: float = 1.0, sigma_min: float = 0.5,
+                     consistency: bool = False, fill: bool = False, fb_a1: float = 0.01, fb_a2: float = 0.5,
+                     fill_r: int = 8, fill_sigma: float = 4.0, fill_passes: int = 2):
     """A start and a range for the engines from two frames alone
     (legacy/optical_flow_temp.m:13-32; defaults: the reference's at scale 1,
     U = floor(6*scale)+1).  The engine's data term compares I1(i, j) with I2 at
@@ -506,11 +508,31 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     engine="super": rank 0's curvature is the SUM over the 4 x 4 block (the
     node's data term sums its 16 pixels, and precisions add) beside the block
     mean of the refined flows; rank k >= 1 takes flow and curvature of the one
-    cheapest pixel, by the rule above."""
-    from .ops import block_match
+    cheapest pixel, by the rule above.
+
+    consistency=True adds a forward-backward check, all of it on the pixel grid
+    (engine="super": before the nodes are formed).  The matcher also runs
+    backward, block_match_init(I2, I1) with the same U, V, ft, sigma and subpixel
+    and one hypothesis, and every forward rank k is checked against that flow by
+    flow_consistency(a1=fb_a1, a2=fb_a2); a missing rank is inconsistent.  Where
+    rank k is inconsistent its flow becomes NaN (keeps the random draw), the cost
+    of a rank k >= 1 becomes +Inf and its curvature 0, so sigma is NaN there.
+    fill=True (needs consistency) gives rank 0 at an inconsistent pixel the value
+    of flow_fill(r=fill_r, sigma=fill_sigma, passes=fill_passes) over the
+    consistent rank-0 pixels instead; a pixel still unfilled stays NaN.  A filled
+    flow is a guess that no curvature certified: its sigma stays NaN, the wide
+    draw.  engine="super": rank 0 of a node is the mean over the non-NaN pixels
+    of its block (NaN when there are none) and its curvature the sum over the
+    consistent pixels; ranks k >= 1 keep the cheapest-pixel rule, which the +Inf
+    costs now steer.  The boolean `consistent` (pixel grid: M x N x H, M x N
+    without hypotheses) is appended as the last element of the return.  With
+    consistency=False every output is what it was without these keywords."""
+    from .ops import block_match, flow_consistency, flow_fill
     sup = engine == "super"
     if sigma_from_cost and not subpixel:
         raise ValueError("block_match_init: sigma_from_cost needs subpixel=True")
+    if fill and not consistency:
+        raise ValueError("block_match_init: fill needs consistency=True")
     if sup and (np.shape(I1)[0] % 4 or np.shape(I1)[1] % 4):
         raise ValueError("super engine: image size must be divisible by 4")
     ranges = dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))
@@ -519,25 +541,54 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     flow, curv = np.asfortranarray(0.0 - out), curv[0] if subpixel else None
     if flow.ndim == 3:  # without hypotheses or subpixel block_match leaves the rank axis out
         flow, cost = flow[..., None], cost[..., None]
+    tail = ()
+    if consistency:
+        back = block_match(I2, I1, U, V, ft, sigma, device=device, host=host, subpixel=subpixel)[0]
+        bwd = np.asfortranarray((0.0 - back).reshape(back.shape[:3], order="F"))
+        # a NaN flow (a missing rank) has no target inside the frame: inconsistent
+        cons = np.stack([flow_consistency(flow[:, :, :, k], bwd, fb_a1, fb_a2, device=device, host=host)[1]
+                         for k in range(flow.shape[3])], axis=2)
+        if fill:
+            flow[:, :, :, 0], state = flow_fill(flow[:, :, :, 0], cons[:, :, 0], fill_r, fill_sigma, fill_passes,
+                                                device=device, host=host)
+            flow[:, :, :, 0][state == 255] = np.nan
+        else:
+            flow[:, :, :, 0][~cons[:, :, 0]] = np.nan
+        for k in range(1, flow.shape[3]):
+            flow[:, :, :, k][~cons[:, :, k]] = np.nan
+            cost[:, :, k][~cons[:, :, k]] = np.inf
+        if curv is not None:
+            curv[np.broadcast_to(~cons[:, :, None, :], curv.shape)] = 0.0
+        tail = (np.asfortranarray(cons[:, :, 0] if hypotheses is None else cons),)
     if sup:
-        nodes = _super_hypotheses(flow, cost, curv)
+        nodes = _super_hypotheses(flow, cost, curv, _mean_of_known if consistency else np.mean)
         flow, curv = nodes if subpixel else (nodes, None)
     if hypotheses is None:
         flow = np.asfortranarray(flow[:, :, :, 0])
     if not sigma_from_cost:
-        return flow, ranges
+        return (flow, ranges) + tail
     if hypotheses is None:
         curv = curv[:, :, :, 0]
     with np.errstate(divide="ignore", invalid="ignore"):
         sig = np.where(curv > 0, np.maximum(np.sqrt(1.0 / (float(lambdad) * curv)), float(sigma_min)), np.nan)
-    return flow, ranges, np.asfortranarray(sig)
+    return (flow, ranges, np.asfortranarray(sig)) + tail
 
 
-def _super_hypotheses(flow, cost, curv=None):
+def _mean_of_known(x, axis):
+    """Mean over the entries that are not NaN; NaN where there are none."""
+    known = ~np.isnan(x)
+    count = known.sum(axis=axis)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(count > 0, np.where(known, x, 0.0).sum(axis=axis) / count, np.nan)
+
+
+def _super_hypotheses(flow, cost, curv=None, mean=np.mean):
     """Pixel hypotheses (M x N x 2 x H, M x N x H) on the super node grid; the
     rule is in block_match_init's docstring.  With curv (shaped as flow) returns
     (flow, curv) on the node grid: the block sum at rank 0, the cheapest pixel's
-    curvature at rank k >= 1 (0 when the whole block misses the rank)."""
+    curvature at rank k >= 1 (0 when the whole block misses the rank).  mean
+    forms rank 0's flow from the block (block_match_init(consistency=True): the
+    mean over the pixels that are not NaN)."""
     M, N, _, H = flow.shape
     m4, n4 = M // 4, N // 4
     # block pixels in column-major order of the block: index i + 4 j
@@ -552,4 +603,4 @@ def _super_hypotheses(flow, cost, curv=None):
         out[:, :, :, 1:] = np.take_along_axis(xb, first[:, :, None, None, :], axis=2)[:, :, 0, :, 1:]
         return out
 
-    return nodes(flow, np.mean) if curv is None else (nodes(flow, np.mean), nodes(curv, np.sum))
+    return nodes(flow, mean) if curv is None else (nodes(flow, mean), nodes(curv, np.sum))

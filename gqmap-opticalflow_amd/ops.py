@@ -8,6 +8,8 @@ imresize        imresize(A, scale) bicubic + antialias (legacy/optical_flow_ctf.
 warp_image      interp2 linear + fillmissing nearest (legacy/optical_flow_ctf.m:30-32)
 block_match     Gaussian-filtered SAD block matching (legacy/optical_flow_temp.m:13-32)
 structure_texture  ROF structure-texture frames (optical_flowSuper.m:7-14, preprocessed=true)
+flow_consistency   forward-backward check of two flows (csrc/gqmap_flowcheck.h)
+flow_fill          rejected pixels refilled from the valid ones around them
 """
 from __future__ import annotations
 
@@ -142,6 +144,61 @@ def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, d
     check(getattr(lib, name)(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), *rank_args,
                              *map(dptr, out), *tail), name)
     return (*out, ms.value) if timed else tuple(out)
+
+
+def flow_consistency(fwd, bwd, a1: float = 0.01, a2: float = 0.5, device: int = 0, host: bool = False,
+                     timed: bool = False):
+    """Forward-backward check (gqmap_flow_consistency).  fwd, bwd: M x N x 2,
+    plane 0 horizontal, in block_match_init's convention: pixel (m, n) of the
+    first frame lies at (m + fwd1, n + fwd0) in the second; bwd lives on the
+    second frame's grid and points back.  Returns (err, mask): err = |fwd +
+    bwd(target)|^2 with bwd sampled bilinearly at the pixel's target, +Inf where
+    the target leaves the frame or is NaN; mask (bool) = err <= a1 (|fwd|^2 +
+    |bwd(target)|^2) + a2.  host=True runs the library's host model of the same
+    arithmetic (no device; bit-identical).  timed=True appends the kernel time
+    in ms."""
+    fwd, bwd = f64(fwd), f64(bwd)
+    if fwd.ndim != 3 or fwd.shape[2] != 2 or bwd.shape != fwd.shape:
+        raise ValueError("flow_consistency: fwd and bwd must be equal-size M x N x 2 flows")
+    M, N, _ = fwd.shape
+    err = np.zeros((M, N), order="F")
+    mask = np.zeros((M, N), dtype=np.uint8, order="F")
+    lib = _lib.load()
+    ms = C.c_double(float("nan"))
+    tail = () if host else (C.cast(C.byref(ms), _lib._D) if timed else None, device)
+    name = "gqmap_flow_consistency" + ("_host" if host else "")
+    check(getattr(lib, name)(dptr(fwd), dptr(bwd), M, N, float(a1), float(a2), dptr(err), u8ptr(mask), *tail), name)
+    out = (err, mask.astype(bool))
+    return (*out, ms.value) if timed else out
+
+
+def flow_fill(flow, mask, r: int = 8, sigma: float = 4.0, passes: int = 2, device: int = 0, host: bool = False,
+              timed: bool = False):
+    """Refill the pixels whose mask is false from the valid pixels around them
+    (gqmap_flow_fill): `passes` Jacobi passes of a normalised convolution with
+    the (2r+1)^2 Gaussian of width sigma; a pixel filled in one pass is valid in
+    the next.  flow: M x N x 2, mask: M x N.  Returns (flow, filled): filled
+    (uint8) is 0 where the pixel was valid on entry, p where pass p filled it and
+    255 where it is still not valid (its flow is then the input's, bit for bit).
+    What flow holds at a pixel that is not valid (NaN included) reaches nothing.
+    host=True runs the library's host model (no device; bit-identical).
+    timed=True appends the kernel time in ms."""
+    flow = f64(flow)
+    if flow.ndim != 3 or flow.shape[2] != 2:
+        raise ValueError("flow_fill: flow must be M x N x 2")
+    M, N, _ = flow.shape
+    if np.shape(mask) != (M, N):
+        raise ValueError(f"flow_fill: mask must be {M}x{N}, got {np.shape(mask)}")
+    mask = np.require((np.asarray(mask) != 0).astype(np.uint8), requirements=["F_CONTIGUOUS", "ALIGNED"])
+    out = np.zeros((M, N, 2), order="F")
+    filled = np.zeros((M, N), dtype=np.uint8, order="F")
+    lib = _lib.load()
+    ms = C.c_double(float("nan"))
+    tail = () if host else (C.cast(C.byref(ms), _lib._D) if timed else None, device)
+    name = "gqmap_flow_fill" + ("_host" if host else "")
+    check(getattr(lib, name)(dptr(flow), u8ptr(mask), M, N, int(r), float(sigma), int(passes), dptr(out), u8ptr(filled),
+                             *tail), name)
+    return (out, filled, ms.value) if timed else (out, filled)
 
 
 def structure_texture(im, theta: float = 0.125, n_iter: int = 100, alp: float = 0.95, device: int = 0,

@@ -326,6 +326,44 @@ gqmap_status gqmap_block_match_refine_host(const double *A, const double *B, int
                                            int V, int ft, double sigma, int H, int sep,
                                            double *flow, double *cost, double *curv);
 
+/* Forward-backward check of two flows (fp64, operation order:
+ * csrc/gqmap_flowcheck.h).  Flows are M x N x 2, column-major, plane 0
+ * horizontal, plane 1 vertical: pixel (m, n) of the first frame lies at
+ * (m + f1, n + f0) in the second (block_match_init's convention and the .flo
+ * ground truth's).  fwd lives on frame 1's grid, bwd on frame 2's and points
+ * back.  Per pixel with (u, v) = fwd(m, n): the target (n + u, m + v) outside
+ * [0, N-1] x [0, M-1] (or NaN) gives err = +Inf, mask = 0; otherwise b = bwd
+ * sampled bilinearly at the target, err = |fwd + b|^2 and mask = err <=
+ * a1 (|fwd|^2 + |b|^2) + a2 (false on NaN).
+ * M, N >= 1; a1, a2 finite and >= 0.  err (M x N doubles) and mask (M x N
+ * bytes, 0 / 1) may each be NULL, not both.
+ * elapsed_ms (may be NULL): kernel time by HIP events, copies excluded. */
+gqmap_status gqmap_flow_consistency(const double *fwd, const double *bwd, int M, int N, double a1,
+                                    double a2, double *err, unsigned char *mask,
+                                    double *elapsed_ms, int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_flow_consistency_host(const double *fwd, const double *bwd, int M, int N,
+                                         double a1, double a2, double *err, unsigned char *mask);
+/* Refill the pixels whose mask is 0 from the valid ones around them: `passes`
+ * Jacobi passes of a normalised convolution with the separable Gaussian
+ * w_i = exp(-(i-r)^2 / 2 / sigma^2), i = 0..2r (rows, then columns, ascending
+ * taps; csrc/gqmap_flowcheck.h).  Per pass a pixel that is not valid and has
+ * a valid pixel in its (2r+1)^2 window takes sum(w flow) / sum(w) over the
+ * valid pixels of the window and is valid from the next pass on; every other
+ * pixel keeps its bits.  What is stored at a pixel that is not valid (NaN, Inf)
+ * reaches nothing.
+ * flow, out: M x N x 2; mask: M x N bytes (non-zero = valid); filled (M x N
+ * bytes, may be NULL): 0 = valid on entry, p = filled in pass p (1-based),
+ * 255 = still not valid.  M, N >= 1, r in [0, 16], sigma finite and > 0, passes
+ * in [1, 8].
+ * elapsed_ms (may be NULL): kernel time by HIP events, copies excluded. */
+gqmap_status gqmap_flow_fill(const double *flow, const unsigned char *mask, int M, int N, int r,
+                             double sigma, int passes, double *out, unsigned char *filled,
+                             double *elapsed_ms, int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_flow_fill_host(const double *flow, const unsigned char *mask, int M, int N, int r,
+                                  double sigma, int passes, double *out, unsigned char *filled);
+
 /* Structure-texture preprocessing: the generator of the frames
  * optical_flowSuper.m:7-14 loads with preprocessed = true (ROF decomposition by
  * Chambolle's dual projection; reference values theta = 1/8, n_iter = 100,
