@@ -40,6 +40,8 @@ EXPORTS = (
     "gqmap_block_match_multi", "gqmap_block_match_multi_host", "gqmap_init_state_flows",
     "gqmap_block_match_refine", "gqmap_block_match_refine_host", "gqmap_init_state_seeded",
     "gqmap_flow_consistency", "gqmap_flow_consistency_host", "gqmap_flow_fill", "gqmap_flow_fill_host",
+    "gqmap_block_match_window", "gqmap_block_match_window_host", "gqmap_block_match_pyramid",
+    "gqmap_block_match_pyramid_host", "gqmap_block_match_reach",
 )
 CTF_MAX_LEVELS = 8
 
@@ -168,6 +170,15 @@ def load():
         "gqmap_block_match_refine_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                                     C.c_int, C.c_int, _D, _D, _D]),
         "gqmap_init_state_seeded": (C.c_int, [vp, _D, _D, C.c_int, C.c_uint64]),
+        "gqmap_block_match_window": (C.c_int, [_D, _D, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _D,
+                                               _D, _D, _D, C.c_int]),
+        "gqmap_block_match_window_host": (C.c_int, [_D, _D, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                    _D, _D, _D]),
+        "gqmap_block_match_pyramid": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, _D, _D, _D, _D, C.c_int]),
+        "gqmap_block_match_pyramid_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                     C.c_int, C.c_int, C.c_int, C.c_int, _D, _D, _D]),
+        "gqmap_block_match_reach": (C.c_int, [C.c_int, C.c_int, C.c_int]),
         "gqmap_flow_consistency": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_double, C.c_double, _D, u8, _D, C.c_int]),
         "gqmap_flow_consistency_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_double, C.c_double, _D, u8]),
         "gqmap_flow_fill": (C.c_int, [_D, u8, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _D, u8, _D, C.c_int]),

@@ -55,6 +55,56 @@
 //                      2 x H, laid out as flow.
 //   missing ranks      flow NaN (bm_nan), cost +Inf, curv 0.0.
 //   cost               the cost at the integer pick, as gqmap_block_match_multi.
+//
+// Per-pixel windows (gqmap_block_match_window): cost and filter as above, the
+// displacement SIGNED: (du, dv) pairs A(m, n) with B(m + du, n + dv), B = 0
+// outside the frame; the index (u, v) above is (du + U, dv + V).  Every bound
+// below satisfies |bound| <= GQ_BM_DMAX.
+//   win                int32, M x N x 4, column-major planes ulo, uhi, vlo, vhi:
+//                      pixel (m, n) considers ulo <= du <= uhi, vlo <= dv <= vhi.
+//                      All pixels under its filter footprint are differenced at
+//                      that same displacement, as in the cost above.
+//   pick               no scan order is implied.  With e = c when c < +Inf and
+//                      e = +Inf otherwise (a NaN cost), a displacement of the
+//                      box replaces the pick when e < best, or e == best and
+//                      (dv, du) is lexicographically smaller (bm_keep_window);
+//                      best starts at +Inf with no pick, which every (dv, du)
+//                      precedes.  That is the first minimum in ascending
+//                      (dv, du), today's u + v (2U+1) order, and on a frame whose
+//                      costs are never < +Inf the first displacement of the box
+//                      with cost +Inf, as bm_keep_allowed leaves it.  Chunking,
+//                      tile width and scan order cannot change a result.
+//   empty window       ulo > uhi or vlo > vhi: flow bm_nan(), cost +Inf, curv 0.0.
+//   flow               ((double)(-dv0), (double)(-du0)), plane 0 horizontal.
+//   subpixel != 0      bm_refine per axis as above; an axis is refinable only if
+//                      both neighbours lie inside the pixel's OWN box (ulo < du0
+//                      < uhi, likewise v); cm, cp are the plain filtered costs;
+//                      flow = ((double)(-dv0) - delta_v, (double)(-du0) -
+//                      delta_u), curv and cost as gqmap_block_match_refine at
+//                      H = 1 (bm_refined_window).
+//   anchor             the box [-U, U] x [-V, V] at every pixel: subpixel = 0 is
+//                      gqmap_block_match bit for bit (flow, cost), subpixel = 1
+//                      gqmap_block_match_refine at H = 1 (flow, cost, curv).
+//
+// Coarse to fine (gqmap_block_match_pyramid; U, V, ft, sigma, levels in [1, 6],
+// r in [0, 4], k in [0, 2], subpixel):
+//   bm_half            ceil(M/2) x ceil(N/2); out(i, j) = ((P(2i, 2j) + P(2i+1,
+//                      2j)) + (P(2i, 2j+1) + P(2i+1, 2j+1))) * 0.25, row 2i+1
+//                      clamped to M-1 and column 2j+1 to N-1.
+//   level l            both frames under bm_half l times; the same ft and sigma.
+//   coarsest           c = levels - 1: every pixel has the box [-Uc, Uc] x
+//                      [-Vc, Vc], Uc = ceil(U / 2^c), Vc likewise, both <=
+//                      GQ_BM_UMAX.
+//   going down         fine pixel (m, n) looks at the integer picks of the coarse
+//                      pixels (m>>1 + a, n>>1 + b), a, b in [-k, k], clamped to
+//                      the coarse grid: ulo = 2 min(du) - r, uhi = 2 max(du) + r,
+//                      v alike (bm_window_up).  A coarse pixel without a pick
+//                      adds nothing; none with a pick: the empty window.
+//   subpixel           level 0 only; coarser levels pass on integer picks.
+//   outputs            level 0's flow, cost and curv.  levels = 1 is the anchor
+//                      above, hence the existing entry points, bit for bit.
+//   reach              Uc 2^c + r (2^c - 1) (bm_reach): the largest |du| the
+//                      scheme can return.
 #pragma once
 #include <math.h>
 
@@ -224,6 +274,151 @@ GQ_BM_HD void bm_refined(int pick, double c0, const BmNear &q, int U, int V, dou
     out[1] = found ? (double)(U - pu) - du : bm_nan();  // umt
     out[2] = kv;
     out[3] = ku;
+}
+
+// ---- per-pixel windows and the coarse-to-fine scheme -------------------------
+
+#define GQ_BM_DMAX 2048                     /* every window bound in [-2048, 2048] */
+#define GQ_BM_CHUNK (2 * GQ_BM_UMAX + 1)    /* displacements per axis of one staged B window */
+#define GQ_BM_LEVELS 6                      /* levels in [1, 6] */
+#define GQ_BM_RMAX 4                        /* r in [0, 4] */
+#define GQ_BM_KMAX 2                        /* k in [0, 2] */
+#define GQ_BM_NOPICK 0x7fffffff             /* no pick: after every key, and the value of both pick planes */
+
+// a signed displacement in one int, ordered as (dv, du) lexicographically
+GQ_BM_HD int bm_key(int du, int dv) { return ((dv + GQ_BM_DMAX) << 13) | (du + GQ_BM_DMAX); }
+GQ_BM_HD int bm_key_du(int key) { return (key & 8191) - GQ_BM_DMAX; }
+GQ_BM_HD int bm_key_dv(int key) { return (key >> 13) - GQ_BM_DMAX; }
+
+// the box {ulo, uhi, vlo, vhi} holds (du, dv)
+GQ_BM_HD bool bm_in_box(const int box[4], int du, int dv)
+{
+    return du >= box[0] && du <= box[1] && dv >= box[2] && dv <= box[3];
+}
+
+// the pick rule of "Per-pixel windows": best starts at +Inf, key at GQ_BM_NOPICK
+GQ_BM_HD void bm_keep_window(bool allowed, double c, int du, int dv, double &best, int &key)
+{
+    const double e = c < INFINITY ? c : INFINITY;
+    const int k = bm_key(du, dv);
+    if (allowed && (e < best || (e == best && k < key))) {
+        best = e;
+        key = k;
+    }
+}
+
+// bm_capture for a signed displacement and a key (GQ_BM_NOPICK has no neighbour in reach)
+GQ_BM_HD void bm_capture_window(int du, int dv, int key, double c, BmNear &q)
+{
+    const int pu = bm_key_du(key), pv = bm_key_dv(key);
+    if (dv == pv) {
+        if (du == pu - 1) q.um = c;
+        if (du == pu + 1) q.up = c;
+    }
+    if (du == pu) {
+        if (dv == pv - 1) q.vm = c;
+        if (dv == pv + 1) q.vp = c;
+    }
+}
+
+// (du, dv) is a neighbour that the refinement of the pick `key` in `box` needs
+GQ_BM_HD bool bm_near_wanted(const int box[4], int du, int dv, int key)
+{
+    const int pu = bm_key_du(key), pv = bm_key_dv(key);
+    if (key == GQ_BM_NOPICK) return false;
+    const bool on_u = dv == pv && (du == pu - 1 || du == pu + 1) && box[0] < pu && pu < box[1];
+    const bool on_v = du == pu && (dv == pv - 1 || dv == pv + 1) && box[2] < pv && pv < box[3];
+    return on_u || on_v;
+}
+
+// bm_refined for a pick in the pixel's own box; subpixel = false leaves the integer flow and curv 0
+GQ_BM_HD void bm_refined_window(int key, double c0, const BmNear &q, const int box[4], bool subpixel, double out[4])
+{
+    const bool found = key != GQ_BM_NOPICK;
+    const int pu = bm_key_du(key), pv = bm_key_dv(key);
+    double du = 0.0, dv = 0.0, ku = 0.0, kv = 0.0;
+    if (subpixel) {
+        bm_refine(q.um, c0, q.up, found && box[0] < pu && pu < box[1], &du, &ku);
+        bm_refine(q.vm, c0, q.vp, found && box[2] < pv && pv < box[3], &dv, &kv);
+        out[0] = found ? (double)(-pv) - dv : bm_nan();
+        out[1] = found ? (double)(-pu) - du : bm_nan();
+    } else {
+        out[0] = found ? (double)(-pv) : bm_nan();
+        out[1] = found ? (double)(-pu) : bm_nan();
+    }
+    out[2] = kv;
+    out[3] = ku;
+}
+
+// one pixel of the half-resolution frame
+GQ_BM_HD double bm_half(const double *P, int M, int N, int i, int j)
+{
+    const int m0 = 2 * i, n0 = 2 * j, m1 = m0 + 1 < M ? m0 + 1 : M - 1, n1 = n0 + 1 < N ? n0 + 1 : N - 1;
+    const double a = P[m0 + (long long)M * n0] + P[m1 + (long long)M * n0];
+    const double b = P[m0 + (long long)M * n1] + P[m1 + (long long)M * n1];
+    return (a + b) * 0.25;
+}
+
+// the box of fine pixel (m, n) from the coarse picks: pick holds the planes du, dv, Mc x Nc each
+GQ_BM_HD void bm_window_up(const int *pick, int Mc, int Nc, int m, int n, int r, int k, int box[4])
+{
+    int ulo = GQ_BM_NOPICK, uhi = -GQ_BM_NOPICK, vlo = GQ_BM_NOPICK, vhi = -GQ_BM_NOPICK;
+    for (int b = -k; b <= k; ++b)
+        for (int a = -k; a <= k; ++a) {
+            int i = (m >> 1) + a, j = (n >> 1) + b;
+            i = i < 0 ? 0 : i > Mc - 1 ? Mc - 1 : i;
+            j = j < 0 ? 0 : j > Nc - 1 ? Nc - 1 : j;
+            const int du = pick[i + (long long)Mc * j], dv = pick[i + (long long)Mc * j + (long long)Mc * Nc];
+            if (du == GQ_BM_NOPICK) continue;
+            ulo = du < ulo ? du : ulo;
+            uhi = du > uhi ? du : uhi;
+            vlo = dv < vlo ? dv : vlo;
+            vhi = dv > vhi ? dv : vhi;
+        }
+    const bool any = ulo != GQ_BM_NOPICK;
+    box[0] = any ? 2 * ulo - r : 1;
+    box[1] = any ? 2 * uhi + r : 0;
+    box[2] = any ? 2 * vlo - r : 1;
+    box[3] = any ? 2 * vhi + r : 0;
+}
+
+GQ_BM_HD int bm_ceil_shift(int x, int c) { return (x + (1 << c) - 1) >> c; }
+
+// the largest displacement the coarse-to-fine scheme can return
+GQ_BM_HD int bm_reach(int U, int levels, int r)
+{
+    const int c = levels - 1;
+    return (bm_ceil_shift(U, c) << c) + r * ((1 << c) - 1);
+}
+
+// Host only: what is wrong with the arguments of the window entry points (nullptr: nothing)
+inline const char *bm_bad_window(int M, int N, int ft, double sigma)
+{
+    if (M < 1 || N < 1) return "empty image";
+    if (ft < 0 || ft > GQ_BM_FTMAX) return "ft outside [0,4]";
+    if (!(sigma > 0) || !isfinite(sigma)) return "sigma must be finite and > 0";
+    return nullptr;
+}
+
+// Host only: a bound of win beyond GQ_BM_DMAX
+inline bool bm_bad_bounds(const int *win, int M, int N)
+{
+    for (long long i = 0; i < 4LL * M * N; ++i)
+        if (win[i] < -GQ_BM_DMAX || win[i] > GQ_BM_DMAX) return true;
+    return false;
+}
+
+// Host only: what is wrong with the arguments of the pyramid entry points (nullptr: nothing)
+inline const char *bm_bad_pyramid(int M, int N, int U, int V, int ft, double sigma, int levels, int r, int k)
+{
+    if (const char *bad = bm_bad_window(M, N, ft, sigma)) return bad;
+    if (levels < 1 || levels > GQ_BM_LEVELS) return "levels outside [1,6]";
+    if (r < 0 || r > GQ_BM_RMAX) return "r outside [0,4]";
+    if (k < 0 || k > GQ_BM_KMAX) return "k outside [0,2]";
+    if (U < 0 || V < 0 || U > GQ_BM_DMAX || V > GQ_BM_DMAX) return "U, V outside [0,2048]";
+    if (bm_ceil_shift(U, levels - 1) > GQ_BM_UMAX || bm_ceil_shift(V, levels - 1) > GQ_BM_UMAX)
+        return "U, V at the coarsest level outside [0,32]";
+    return nullptr;
 }
 
 }  // namespace gq

@@ -209,6 +209,7 @@ static int bm_choose_cols(int M, int N, int U, int V, int ft, int cus)
 
 // tile columns forced by gqmap_debug_block_match_cols (0: chosen from the grid)
 static int g_bm_cols = 0;
+int bm_forced_cols() { return g_bm_cols; }  // gqmap_blockmatch_window.hip follows the same debug switch
 
 // H = 0: the single mode (gqmap_block_match); H >= 1: multi, or with refine the refine mode (dcurv may be null)
 template <int NPT>

@@ -475,7 +475,8 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
                      hypotheses: int | None = None, sep: int = 2, subpixel: bool = False,
                      sigma_from_cost: bool = False, lambdad: float = 1.0, sigma_min: float = 0.5,
                      consistency: bool = False, fill: bool = False, fb_a1: float = 0.01, fb_a2: float = 0.5,
-                     fill_r: int = 8, fill_sigma: float = 4.0, fill_passes: int = 2):
+                     fill_r: int = 8, fill_sigma: float = 4.0, fill_passes: int = 2, levels: int = 1, pyr_r: int = 1,
+                     pyr_k: int = 1):
     """A start and a range for the engines from two frames alone
     (legacy/optical_flow_temp.m:13-32; defaults: the reference's at scale 1,
     U = floor(6*scale)+1).  The engine's data term compares I1(i, j) with I2 at
@@ -526,8 +527,17 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     consistent pixels; ranks k >= 1 keep the cheapest-pixel rule, which the +Inf
     costs now steer.  The boolean `consistent` (pixel grid: M x N x H, M x N
     without hypotheses) is appended as the last element of the return.  With
-    consistency=False every output is what it was without these keywords."""
-    from .ops import block_match, flow_consistency, flow_fill
+    consistency=False every output is what it was without these keywords.
+
+    levels > 1 takes rank 0 from the coarse-to-fine matcher instead,
+    block_match_pyramid(levels=levels, r=pyr_r, k=pyr_k), forward and, with
+    consistency=True, backward; subpixel, sigma_from_cost, consistency, fill and
+    engine="super" work on it as on rank 0 above, shapes unchanged.  U and V may
+    then exceed 32 (ceil(U / 2^(levels-1)) <= 32) and the ranges become
+    +-block_match_reach(V, levels, pyr_r) / +-block_match_reach(U, levels, pyr_r).
+    Further hypotheses are out of its scope: hypotheses > 1 raises ValueError.
+    With levels=1 every output is what it was without these keywords."""
+    from .ops import block_match, block_match_pyramid, block_match_reach, flow_consistency, flow_fill
     sup = engine == "super"
     if sigma_from_cost and not subpixel:
         raise ValueError("block_match_init: sigma_from_cost needs subpixel=True")
@@ -535,15 +545,29 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
         raise ValueError("block_match_init: fill needs consistency=True")
     if sup and (np.shape(I1)[0] % 4 or np.shape(I1)[1] % 4):
         raise ValueError("super engine: image size must be divisible by 4")
-    ranges = dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))
-    out, cost, *curv = block_match(I1, I2, U, V, ft, sigma, device=device, host=host, hypotheses=hypotheses, sep=sep,
-                                   subpixel=subpixel)
+    if levels > 1 and hypotheses is not None and hypotheses > 1:
+        raise ValueError("block_match_init: levels > 1 yields one hypothesis per pixel")
+    if levels > 1:
+        ru, rv = (float(block_match_reach(x, levels, pyr_r)) for x in (U, V))
+        ranges = dict(minu=-rv, maxu=rv, minv=-ru, maxv=ru)
+
+        def match(A, B, **kw):  # rank 0 with the rank axis block_match gives it
+            got = block_match_pyramid(A, B, U, V, ft, sigma, levels, pyr_r, pyr_k, subpixel=subpixel, device=device,
+                                      host=host)
+            ranked = hypotheses is not None or subpixel
+            return tuple(np.asfortranarray(a[..., None]) for a in got) if ranked else got
+    else:
+        ranges = dict(minu=float(-V), maxu=float(V), minv=float(-U), maxv=float(U))
+
+        def match(A, B, **kw):
+            return block_match(A, B, U, V, ft, sigma, device=device, host=host, subpixel=subpixel, **kw)
+    out, cost, *curv = match(I1, I2, hypotheses=hypotheses, sep=sep)
     flow, curv = np.asfortranarray(0.0 - out), curv[0] if subpixel else None
     if flow.ndim == 3:  # without hypotheses or subpixel block_match leaves the rank axis out
         flow, cost = flow[..., None], cost[..., None]
     tail = ()
     if consistency:
-        back = block_match(I2, I1, U, V, ft, sigma, device=device, host=host, subpixel=subpixel)[0]
+        back = match(I2, I1)[0]
         bwd = np.asfortranarray((0.0 - back).reshape(back.shape[:3], order="F"))
         # a NaN flow (a missing rank) has no target inside the frame: inconsistent
         cons = np.stack([flow_consistency(flow[:, :, :, k], bwd, fb_a1, fb_a2, device=device, host=host)[1]

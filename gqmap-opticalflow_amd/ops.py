@@ -7,6 +7,8 @@ gauss_hermite   GaussHermite_2.m (host)
 imresize        imresize(A, scale) bicubic + antialias (legacy/optical_flow_ctf.m:26-29)
 warp_image      interp2 linear + fillmissing nearest (legacy/optical_flow_ctf.m:30-32)
 block_match     Gaussian-filtered SAD block matching (legacy/optical_flow_temp.m:13-32)
+block_match_window   the same cost over a search window per pixel (csrc/gqmap_blockmatch.h)
+block_match_pyramid  coarse-to-fine block matching on block_match_window
 structure_texture  ROF structure-texture frames (optical_flowSuper.m:7-14, preprocessed=true)
 flow_consistency   forward-backward check of two flows (csrc/gqmap_flowcheck.h)
 flow_fill          rejected pixels refilled from the valid ones around them
@@ -144,6 +146,71 @@ def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, d
     check(getattr(lib, name)(dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), *rank_args,
                              *map(dptr, out), *tail), name)
     return (*out, ms.value) if timed else tuple(out)
+
+
+def _match_outputs(lib, name, host, timed, device, M, N, subpixel, head):
+    """The (flow, cost[, curv][, ms]) tail of the window and pyramid calls."""
+    flow, cost, curv = np.zeros((M, N, 2), order="F"), np.zeros((M, N), order="F"), np.zeros((M, N, 2), order="F")
+    ms = C.c_double(float("nan"))
+    tail = () if host else (C.cast(C.byref(ms), _lib._D) if timed else None, device)
+    name += "_host" if host else ""
+    check(getattr(lib, name)(*head, int(bool(subpixel)), dptr(flow), dptr(cost), dptr(curv) if subpixel else None,
+                             *tail), name)
+    out = (flow, cost, curv) if subpixel else (flow, cost)
+    return (*out, ms.value) if timed else out
+
+
+def block_match_window(A, B, win, ft: int = 3, sigma: float = 1.7, subpixel: bool = False, device: int = 0,
+                       host: bool = False, timed: bool = False):
+    """block_match with a search window per pixel (gqmap_block_match_window).
+    win: integer M x N x 4 = (ulo, uhi, vlo, vhi), bounds in [-2048, 2048]: pixel
+    (m, n) pairs A(m, n) with B(m + du, n + dv) over ulo <= du <= uhi, vlo <= dv
+    <= vhi and takes the first minimum in ascending (dv, du).  Returns (flow
+    M x N x 2 = (-dv0, -du0), cost M x N), laid out and signed as block_match's;
+    a pixel with an empty window is NaN in flow and +Inf in cost.
+    subpixel=True returns (flow, cost, curv): the parabola of
+    block_match(subpixel=True) per axis, on an axis whose two neighbours lie inside
+    the pixel's own window.  With win = [-U, U] x [-V, V] everywhere the results
+    are block_match's, bit for bit.  host=True runs the library's host model (no
+    device; bit-identical); timed=True appends the kernel time in ms."""
+    A, B = f64(A), f64(B)
+    if A.ndim != 2 or A.shape != B.shape:
+        raise ValueError("block_match_window: A and B must be equal-size 2-D images")
+    M, N = A.shape
+    if np.shape(win) != (M, N, 4):
+        raise ValueError(f"block_match_window: win must be {M}x{N}x4, got {np.shape(win)}")
+    win = np.require(np.asarray(win, dtype=np.int32), requirements=["F_CONTIGUOUS", "ALIGNED"])
+    head = (dptr(A), dptr(B), win.ctypes.data_as(C.POINTER(C.c_int)), M, N, int(ft), float(sigma))
+    return _match_outputs(_lib.load(), "gqmap_block_match_window", host, timed, device, M, N, subpixel, head)
+
+
+def block_match_reach(U: int, levels: int, r: int) -> int:
+    """The largest displacement along an axis that block_match_pyramid(U, ..., levels, r) can return."""
+    reach = int(_lib.load().gqmap_block_match_reach(int(U), int(levels), int(r)))
+    if reach < 0:
+        raise ValueError(f"block_match_reach: U={U} levels={levels} r={r} out of range")
+    return reach
+
+
+def block_match_pyramid(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, levels: int = 2, r: int = 1,
+                        k: int = 1, subpixel: bool = False, device: int = 0, host: bool = False, timed: bool = False):
+    """Coarse-to-fine block matching (gqmap_block_match_pyramid).  Both frames
+    are halved levels - 1 times (2 x 2 means); the coarsest level searches
+    +-ceil(U / 2^(levels-1)) x +-ceil(V / 2^(levels-1)) (each <= 32, so U and V may
+    exceed 32), and every finer level searches, per pixel, the box spanned by
+    twice the picks of the (2k+1) x (2k+1) coarse pixels around it, widened by r
+    (block_match_window).  levels in 1..6, r in 0..4, k in 0..2.  Returns (flow,
+    cost) of level 0, or (flow, cost, curv) with subpixel=True (applied at level 0
+    only), shaped as block_match_window's; levels=1 is block_match, bit for bit.
+    The displacements returned lie within +-block_match_reach(U, levels, r).
+    host=True runs the library's host model (no device; bit-identical);
+    timed=True appends the time of all kernels of the call in ms."""
+    A, B = f64(A), f64(B)
+    if A.ndim != 2 or A.shape != B.shape:
+        raise ValueError("block_match_pyramid: A and B must be equal-size 2-D images")
+    M, N = A.shape
+    head = (dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), int(levels), int(r), int(k))
+    return _match_outputs(_lib.load(), "gqmap_block_match_pyramid", host, timed, device, M, N, subpixel, head)
 
 
 def flow_consistency(fwd, bwd, a1: float = 0.01, a2: float = 0.5, device: int = 0, host: bool = False,

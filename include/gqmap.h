@@ -326,6 +326,56 @@ gqmap_status gqmap_block_match_refine_host(const double *A, const double *B, int
                                            int V, int ft, double sigma, int H, int sep,
                                            double *flow, double *cost, double *curv);
 
+/* Block matching with a search window per pixel (arithmetic:
+ * csrc/gqmap_blockmatch.h, "Per-pixel windows").  The displacement is signed:
+ * (du, dv) pairs A(m, n) with B(m + du, n + dv), B zero outside the frame;
+ * gqmap_block_match's index (u, v) is (du + U, dv + V).
+ * win: int32, M x N x 4, column-major planes ulo, uhi, vlo, vhi, every bound in
+ * [-2048, 2048].  Pixel (m, n) considers ulo <= du <= uhi, vlo <= dv <= vhi; its
+ * pick is the first minimum in ascending (dv, du), stated as a tie rule (a
+ * smaller cost, or an equal cost at a lexicographically smaller (dv, du)), so
+ * tiling and scan order show in no result.  An empty window (ulo > uhi or
+ * vlo > vhi): flow NaN, cost +Inf, curv 0.
+ * flow (M x N x 2) = (-dv0, -du0), plane 0 horizontal as gqmap_block_match's;
+ * cost (M x N, may be NULL) the cost at the pick.  subpixel != 0: the parabola
+ * of gqmap_block_match_refine per axis, refinable only when both neighbours lie
+ * inside the pixel's own box; curv (M x N x 2, may be NULL) as there, 0 with
+ * subpixel = 0.  With the box [-U, U] x [-V, V] at every pixel the results are
+ * gqmap_block_match's (subpixel = 0) and gqmap_block_match_refine's at H = 1
+ * (subpixel != 0), bit for bit.
+ * ft in [0,4], sigma finite and > 0, M, N >= 1.  The work follows the windows:
+ * a tile evaluates the displacements that one of its pixels asks for.
+ * elapsed_ms (may be NULL): kernel time by HIP events, copies excluded. */
+gqmap_status gqmap_block_match_window(const double *A, const double *B, const int *win, int M,
+                                      int N, int ft, double sigma, int subpixel, double *flow,
+                                      double *cost, double *curv, double *elapsed_ms, int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_block_match_window_host(const double *A, const double *B, const int *win, int M,
+                                           int N, int ft, double sigma, int subpixel, double *flow,
+                                           double *cost, double *curv);
+/* Coarse-to-fine block matching ("Coarse to fine" of csrc/gqmap_blockmatch.h).
+ * Level l holds both frames halved l times (2 x 2 means, ceil sizes, the last
+ * row / column repeated).  The coarsest level c = levels - 1 searches the box
+ * [-Uc, Uc] x [-Vc, Vc], Uc = ceil(U / 2^c) <= 32, Vc likewise; each finer level
+ * gives pixel (m, n) the box spanned by twice the integer picks of the coarse
+ * pixels (m>>1 + a, n>>1 + b), a, b in [-k, k] (clamped to the grid), widened
+ * by r, and runs gqmap_block_match_window on it.  Only level 0 applies subpixel.
+ * levels in [1,6], r in [0,4], k in [0,2]; U, V may exceed 32.  levels = 1 is
+ * gqmap_block_match / gqmap_block_match_refine at H = 1, bit for bit.
+ * flow, cost, curv as gqmap_block_match_window's.  Frames, picks and windows of
+ * all levels stay on the device; elapsed_ms covers all kernels of the call. */
+gqmap_status gqmap_block_match_pyramid(const double *A, const double *B, int M, int N, int U, int V,
+                                       int ft, double sigma, int levels, int r, int k,
+                                       int subpixel, double *flow, double *cost, double *curv,
+                                       double *elapsed_ms, int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_block_match_pyramid_host(const double *A, const double *B, int M, int N, int U,
+                                            int V, int ft, double sigma, int levels, int r, int k,
+                                            int subpixel, double *flow, double *cost, double *curv);
+/* ceil(U / 2^c) 2^c + r (2^c - 1), c = levels - 1: the largest displacement along
+ * an axis that gqmap_block_match_pyramid can return (-1: argument out of range) */
+int gqmap_block_match_reach(int U, int levels, int r);
+
 /* Forward-backward check of two flows (fp64, operation order:
  * csrc/gqmap_flowcheck.h).  Flows are M x N x 2, column-major, plane 0
  * horizontal, plane 1 vertical: pixel (m, n) of the first frame lies at
