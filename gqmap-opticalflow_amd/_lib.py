@@ -42,6 +42,8 @@ EXPORTS = (
     "gqmap_flow_consistency", "gqmap_flow_consistency_host", "gqmap_flow_fill", "gqmap_flow_fill_host",
     "gqmap_block_match_window", "gqmap_block_match_window_host", "gqmap_block_match_pyramid",
     "gqmap_block_match_pyramid_host", "gqmap_block_match_reach",
+    "gqmap_block_match_window_multi", "gqmap_block_match_window_multi_host", "gqmap_block_match_pyramid_multi",
+    "gqmap_block_match_pyramid_multi_host",
 )
 CTF_MAX_LEVELS = 8
 
@@ -179,6 +181,16 @@ def load():
         "gqmap_block_match_pyramid_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                                      C.c_int, C.c_int, C.c_int, C.c_int, _D, _D, _D]),
         "gqmap_block_match_reach": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+        "gqmap_block_match_window_multi": (C.c_int, [_D, _D, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                     C.c_int, C.c_int, _D, _D, _D, _D, C.c_int]),
+        "gqmap_block_match_window_multi_host": (C.c_int, [_D, _D, P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double,
+                                                          C.c_int, C.c_int, C.c_int, _D, _D, _D]),
+        "gqmap_block_match_pyramid_multi": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _D, _D, _D,
+                                                      _D, C.c_int]),
+        "gqmap_block_match_pyramid_multi_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                           C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                           C.c_int, _D, _D, _D]),
         "gqmap_flow_consistency": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_double, C.c_double, _D, u8, _D, C.c_int]),
         "gqmap_flow_consistency_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_double, C.c_double, _D, u8]),
         "gqmap_flow_fill": (C.c_int, [_D, u8, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _D, u8, _D, C.c_int]),

@@ -105,6 +105,45 @@
 //                      above, hence the existing entry points, bit for bit.
 //   reach              Uc 2^c + r (2^c - 1) (bm_reach): the largest |du| the
 //                      scheme can return.
+//
+// Ranked windows (gqmap_block_match_window_multi): cost, filter, signed
+// displacement and GQ_BM_DMAX as in "Per-pixel windows"; on top of them H in
+// [1, GQ_BM_HMAX] and sep in [1, 2 GQ_BM_UMAX + 1] (bm_bad_multi).
+//   win                int32, M x N x 4 x H, rank slowest; slice j is laid out as
+//                      `win` above and holds box j of every pixel.
+//   pick               rank j applies the rule of bm_keep_window to the
+//                      displacements of ITS box j that also satisfy max(|du -
+//                      du_i|, |dv - dv_i|) >= sep for the pick (du_i, dv_i) of
+//                      every earlier rank i < j that has one (bm_far_key, the
+//                      signed sibling of bm_far).
+//   missing ranks      box j empty, or nothing in it allowed: flow bm_nan(), cost
+//                      +Inf, curv 0.0.  A missing rank excludes nothing, and
+//                      later ranks go on: their boxes differ.
+//   subpixel != 0      per rank, bm_refine per axis; an axis is refinable only
+//                      when both neighbours lie in that rank's own box; cm, cp are
+//                      the plain filtered costs, whether or not the separation
+//                      would allow them (bm_refined_window, unchanged).
+//   outputs            flow and curv M x N x 2 x H, cost M x N x H, rank slowest;
+//                      signs and planes as gqmap_block_match_window's.  Scan
+//                      order, chunking and tile width appear in no result.
+//   identities         H = 1 is gqmap_block_match_window.  Rank 0 is
+//                      gqmap_block_match_window on box 0 for any H and sep.  All H
+//                      boxes [-U, U] x [-V, V]: subpixel = 0 is
+//                      gqmap_block_match_multi, subpixel = 1
+//                      gqmap_block_match_refine, at the same H and sep, missing
+//                      ranks included (equal boxes make the allowed sets shrink).
+//
+// Ranked coarse to fine (gqmap_block_match_pyramid_multi): levels, bm_half, Uc,
+// Vc, r, k and bm_reach as in "Coarse to fine"; H and sep as above.
+//   coarsest           all H boxes are [-Uc, Uc] x [-Vc, Vc].
+//   going down         box j of a fine pixel is bm_window_up over the coarse
+//                      level's rank-j pick planes; a coarse pixel that misses
+//                      rank j adds nothing.
+//   every level        runs "Ranked windows" with the same H and sep; only level
+//                      0 applies subpixel; the outputs are level 0's.
+//   identities         H = 1 is gqmap_block_match_pyramid, and so is rank 0 at
+//                      any H and sep: rank 0 depends on rank-0 picks only, level
+//                      by level.  levels = 1 is the equal-boxes identity above.
 #pragma once
 #include <math.h>
 
@@ -305,6 +344,15 @@ GQ_BM_HD void bm_keep_window(bool allowed, double c, int du, int dv, double &bes
         best = e;
         key = k;
     }
+}
+
+// bm_far for a signed displacement and the key of an earlier rank; a missing rank (GQ_BM_NOPICK) excludes nothing
+GQ_BM_HD bool bm_far_key(int du, int dv, int key, int sep)
+{
+    int au = du - bm_key_du(key), av = dv - bm_key_dv(key);
+    au = au < 0 ? -au : au;
+    av = av < 0 ? -av : av;
+    return key == GQ_BM_NOPICK || (au > av ? au : av) >= sep;
 }
 
 // bm_capture for a signed displacement and a key (GQ_BM_NOPICK has no neighbour in reach)

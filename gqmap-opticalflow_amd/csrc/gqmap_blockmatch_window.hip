@@ -43,7 +43,8 @@ constexpr int BMW_THREADS = BMW_TM * BMW_GROUPS;
 constexpr int BMW_CHUNK_DEFAULT = 17;  // chunk extent when the windows' extent is not known to the host
 
 // LDS doubles of one workgroup: A tile, B window of one chunk, two T tiles; k_block_match's at CU = 2U+1, CV = 2V+1
-static size_t bmw_lds_doubles(int TN, int CU, int CV, int ft)
+// (also the tile of k_block_match_ranked, gqmap_blockmatch_ranked.hip)
+size_t bmw_lds_doubles(int TN, int CU, int CV, int ft)
 {
     const size_t AH = BMW_TM + 2 * ft, AW = TN + 2 * ft;
     return AH * AW + (AH + CU - 1) * (AW + CV - 1) + 2 * (size_t)BMW_TM * AW;
@@ -254,8 +255,23 @@ __global__ __launch_bounds__(256) void k_bm_window_up(const int *__restrict__ pi
     }
 }
 
+// host-side launchers of the two helper kernels, for the ranked pyramid (gqmap_blockmatch_ranked.hip)
+hipError_t bmw_half_launch(const double *dP, int M, int N, double *dout, int Mh, int Nh, hipStream_t s)
+{
+    const dim3 grid((unsigned)((Mh + 255) / 256), (unsigned)Nh);
+    k_bm_half<<<grid, 256, 0, s>>>(dP, M, N, dout, Mh, Nh);
+    return hipGetLastError();
+}
+
+hipError_t bmw_window_up_launch(const int *dpick, int Mc, int Nc, int M, int N, int r, int k, int *dwin, hipStream_t s)
+{
+    const dim3 grid((unsigned)((M + 255) / 256), (unsigned)N);
+    k_bm_window_up<<<grid, 256, 0, s>>>(dpick, Mc, Nc, M, N, r, k, dwin);
+    return hipGetLastError();
+}
+
 // tile width by the rule of bm_choose_cols (gqmap_blockmatch.hip): the widest that keeps 4 workgroups per CU
-static int bmw_choose_cols(int M, int N, int CU, int CV, int ft, int cus)
+int bmw_choose_cols(int M, int N, int CU, int CV, int ft, int cus)
 {
     const double lds_cu = 160.0 * 1024, tiles_m = (M + BMW_TM - 1) / BMW_TM;
     int cols = 8;
@@ -277,6 +293,11 @@ static int bmw_choose_cols(int M, int N, int CU, int CV, int ft, int cus)
 static int g_bmw_cu = 0, g_bmw_cv = 0;
 static bool g_bmw_stats = false;
 static double g_bmw_last[GQ_BM_LEVELS][5];
+
+// the same switches and counters for gqmap_blockmatch_ranked.hip
+void bmw_forced_chunk(int *cu, int *cv) { *cu = g_bmw_cu, *cv = g_bmw_cv; }
+bool bmw_stats_on() { return g_bmw_stats; }
+double *bmw_stats_last(int level) { return g_bmw_last[level]; }
 
 template <int NPT>
 static hipError_t bmw_launch(const double *dA, const double *dB, const int *dwin, int4 cbox, int M, int N, int ft,

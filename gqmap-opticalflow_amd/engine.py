@@ -476,7 +476,7 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
                      sigma_from_cost: bool = False, lambdad: float = 1.0, sigma_min: float = 0.5,
                      consistency: bool = False, fill: bool = False, fb_a1: float = 0.01, fb_a2: float = 0.5,
                      fill_r: int = 8, fill_sigma: float = 4.0, fill_passes: int = 2, levels: int = 1, pyr_r: int = 1,
-                     pyr_k: int = 1):
+                     pyr_k: int = 1, pyr_ranked: bool = False):
     """A start and a range for the engines from two frames alone
     (legacy/optical_flow_temp.m:13-32; defaults: the reference's at scale 1,
     U = floor(6*scale)+1).  The engine's data term compares I1(i, j) with I2 at
@@ -535,8 +535,18 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     engine="super" work on it as on rank 0 above, shapes unchanged.  U and V may
     then exceed 32 (ceil(U / 2^(levels-1)) <= 32) and the ranges become
     +-block_match_reach(V, levels, pyr_r) / +-block_match_reach(U, levels, pyr_r).
-    Further hypotheses are out of its scope: hypotheses > 1 raises ValueError.
-    With levels=1 every output is what it was without these keywords."""
+    By default it yields one hypothesis per pixel: hypotheses > 1 raises
+    ValueError.  With levels=1 every output is what it was without these
+    keywords.
+
+    pyr_ranked=True (with levels > 1 and hypotheses=H) takes rank k from the
+    ranked coarse-to-fine matcher, block_match_pyramid(levels=levels, r=pyr_r,
+    k=pyr_k, hypotheses=H, sep=sep): every rank is handed down the levels in a
+    box of its own, rank 0 is the flow without pyr_ranked, and a rank missing at
+    a pixel stays NaN.  Only the forward pass is ranked; the backward pass of
+    consistency=True stays the plain pyramid with one hypothesis.  subpixel,
+    sigma_from_cost, consistency, fill and engine="super" apply to the ranks as
+    they do at levels=1, and the ranges stay +-block_match_reach."""
     from .ops import block_match, block_match_pyramid, block_match_reach, flow_consistency, flow_fill
     sup = engine == "super"
     if sigma_from_cost and not subpixel:
@@ -545,13 +555,16 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
         raise ValueError("block_match_init: fill needs consistency=True")
     if sup and (np.shape(I1)[0] % 4 or np.shape(I1)[1] % 4):
         raise ValueError("super engine: image size must be divisible by 4")
-    if levels > 1 and hypotheses is not None and hypotheses > 1:
-        raise ValueError("block_match_init: levels > 1 yields one hypothesis per pixel")
+    if levels > 1 and hypotheses is not None and hypotheses > 1 and not pyr_ranked:
+        raise ValueError("block_match_init: levels > 1 yields one hypothesis per pixel (pyr_ranked=True: one per rank)")
     if levels > 1:
         ru, rv = (float(block_match_reach(x, levels, pyr_r)) for x in (U, V))
         ranges = dict(minu=-rv, maxu=rv, minv=-ru, maxv=ru)
 
         def match(A, B, **kw):  # rank 0 with the rank axis block_match gives it
+            if pyr_ranked and kw.get("hypotheses") is not None:  # the forward pass: the ranks come with their axis
+                return block_match_pyramid(A, B, U, V, ft, sigma, levels, pyr_r, pyr_k, subpixel=subpixel,
+                                           device=device, host=host, **kw)
             got = block_match_pyramid(A, B, U, V, ft, sigma, levels, pyr_r, pyr_k, subpixel=subpixel, device=device,
                                       host=host)
             ranked = hypotheses is not None or subpixel

@@ -148,20 +148,31 @@ def block_match(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, d
     return (*out, ms.value) if timed else tuple(out)
 
 
-def _match_outputs(lib, name, host, timed, device, M, N, subpixel, head):
-    """The (flow, cost[, curv][, ms]) tail of the window and pyramid calls."""
-    flow, cost, curv = np.zeros((M, N, 2), order="F"), np.zeros((M, N), order="F"), np.zeros((M, N, 2), order="F")
+def _match_outputs(lib, name, host, timed, device, M, N, subpixel, head, ranks=()):
+    """The (flow, cost[, curv][, ms]) tail of the window and pyramid calls; ranks = (H, sep) for the ranked entry points."""
+    tail_shape = ranks[:1]
+    flow, cost, curv = (np.zeros(s + tail_shape, order="F") for s in ((M, N, 2), (M, N), (M, N, 2)))
     ms = C.c_double(float("nan"))
     tail = () if host else (C.cast(C.byref(ms), _lib._D) if timed else None, device)
-    name += "_host" if host else ""
-    check(getattr(lib, name)(*head, int(bool(subpixel)), dptr(flow), dptr(cost), dptr(curv) if subpixel else None,
-                             *tail), name)
+    name += ("_multi" if ranks else "") + ("_host" if host else "")
+    check(getattr(lib, name)(*head, *ranks, int(bool(subpixel)), dptr(flow), dptr(cost),
+                             dptr(curv) if subpixel else None, *tail), name)
     out = (flow, cost, curv) if subpixel else (flow, cost)
     return (*out, ms.value) if timed else out
 
 
+def _ranks(who, hypotheses, sep):
+    """(H, sep) of a ranked call, () without hypotheses."""
+    if hypotheses is None:
+        return ()
+    H = int(hypotheses)
+    if not 1 <= H <= 4:  # the shapes depend on it; the library checks the rest
+        raise ValueError(f"{who}: hypotheses must be in 1..4, got {hypotheses}")
+    return (H, int(sep))
+
+
 def block_match_window(A, B, win, ft: int = 3, sigma: float = 1.7, subpixel: bool = False, device: int = 0,
-                       host: bool = False, timed: bool = False):
+                       host: bool = False, timed: bool = False, hypotheses: int | None = None, sep: int = 2):
     """block_match with a search window per pixel (gqmap_block_match_window).
     win: integer M x N x 4 = (ulo, uhi, vlo, vhi), bounds in [-2048, 2048]: pixel
     (m, n) pairs A(m, n) with B(m + du, n + dv) over ulo <= du <= uhi, vlo <= dv
@@ -172,16 +183,31 @@ def block_match_window(A, B, win, ft: int = 3, sigma: float = 1.7, subpixel: boo
     block_match(subpixel=True) per axis, on an axis whose two neighbours lie inside
     the pixel's own window.  With win = [-U, U] x [-V, V] everywhere the results
     are block_match's, bit for bit.  host=True runs the library's host model (no
-    device; bit-identical); timed=True appends the kernel time in ms."""
+    device; bit-identical); timed=True appends the kernel time in ms.
+
+    hypotheses=H (1..4) returns H ranked picks (gqmap_block_match_window_multi):
+    win is M x N x 4 x H, a box per rank (an M x N x 4 window is given to every
+    rank), and rank j is the pick above over the displacements of box j at least
+    `sep` away (larger of the row and column distance) from the pick of every
+    earlier rank that has one.  flow and curv are M x N x 2 x H, cost M x N x H,
+    as block_match(hypotheses=H)'s; a rank whose box is empty, or in which
+    nothing is allowed, is NaN / +Inf / 0, excludes nothing, and later ranks go
+    on.  Rank 0 is the call without hypotheses on box 0; with the same box
+    [-U, U] x [-V, V] at every rank the results are block_match(hypotheses=H,
+    sep=sep)'s, bit for bit."""
     A, B = f64(A), f64(B)
     if A.ndim != 2 or A.shape != B.shape:
         raise ValueError("block_match_window: A and B must be equal-size 2-D images")
     M, N = A.shape
-    if np.shape(win) != (M, N, 4):
-        raise ValueError(f"block_match_window: win must be {M}x{N}x4, got {np.shape(win)}")
+    ranks = _ranks("block_match_window", hypotheses, sep)
+    if ranks and np.shape(win) == (M, N, 4):
+        win = np.repeat(np.asarray(win)[..., None], ranks[0], axis=3)
+    if np.shape(win) != (M, N, 4) + ranks[:1]:
+        want = "x".join(map(str, (M, N, 4) + ranks[:1]))
+        raise ValueError(f"block_match_window: win must be {want}, got {np.shape(win)}")
     win = np.require(np.asarray(win, dtype=np.int32), requirements=["F_CONTIGUOUS", "ALIGNED"])
     head = (dptr(A), dptr(B), win.ctypes.data_as(C.POINTER(C.c_int)), M, N, int(ft), float(sigma))
-    return _match_outputs(_lib.load(), "gqmap_block_match_window", host, timed, device, M, N, subpixel, head)
+    return _match_outputs(_lib.load(), "gqmap_block_match_window", host, timed, device, M, N, subpixel, head, ranks)
 
 
 def block_match_reach(U: int, levels: int, r: int) -> int:
@@ -193,7 +219,8 @@ def block_match_reach(U: int, levels: int, r: int) -> int:
 
 
 def block_match_pyramid(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, levels: int = 2, r: int = 1,
-                        k: int = 1, subpixel: bool = False, device: int = 0, host: bool = False, timed: bool = False):
+                        k: int = 1, subpixel: bool = False, device: int = 0, host: bool = False, timed: bool = False,
+                        hypotheses: int | None = None, sep: int = 2):
     """Coarse-to-fine block matching (gqmap_block_match_pyramid).  Both frames
     are halved levels - 1 times (2 x 2 means); the coarsest level searches
     +-ceil(U / 2^(levels-1)) x +-ceil(V / 2^(levels-1)) (each <= 32, so U and V may
@@ -204,13 +231,22 @@ def block_match_pyramid(A, B, U: int = 7, V: int = 7, ft: int = 3, sigma: float 
     only), shaped as block_match_window's; levels=1 is block_match, bit for bit.
     The displacements returned lie within +-block_match_reach(U, levels, r).
     host=True runs the library's host model (no device; bit-identical);
-    timed=True appends the time of all kernels of the call in ms."""
+    timed=True appends the time of all kernels of the call in ms.
+
+    hypotheses=H (1..4) carries H ranked picks through the levels
+    (gqmap_block_match_pyramid_multi): every level runs
+    block_match_window(hypotheses=H, sep=sep), all boxes equal at the coarsest,
+    and box j of a finer pixel comes from the rank-j picks of the coarse pixels
+    around it, so every rank keeps a narrow box of its own.  The outputs carry
+    the rank axis as block_match_window(hypotheses=H)'s.  Rank 0 is the call
+    without hypotheses, bit for bit; levels=1 is block_match(hypotheses=H)."""
     A, B = f64(A), f64(B)
     if A.ndim != 2 or A.shape != B.shape:
         raise ValueError("block_match_pyramid: A and B must be equal-size 2-D images")
     M, N = A.shape
+    ranks = _ranks("block_match_pyramid", hypotheses, sep)
     head = (dptr(A), dptr(B), M, N, int(U), int(V), int(ft), float(sigma), int(levels), int(r), int(k))
-    return _match_outputs(_lib.load(), "gqmap_block_match_pyramid", host, timed, device, M, N, subpixel, head)
+    return _match_outputs(_lib.load(), "gqmap_block_match_pyramid", host, timed, device, M, N, subpixel, head, ranks)
 
 
 def flow_consistency(fwd, bwd, a1: float = 0.01, a2: float = 0.5, device: int = 0, host: bool = False,

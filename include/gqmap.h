@@ -372,6 +372,54 @@ gqmap_status gqmap_block_match_pyramid(const double *A, const double *B, int M, 
 gqmap_status gqmap_block_match_pyramid_host(const double *A, const double *B, int M, int N, int U,
                                             int V, int ft, double sigma, int levels, int r, int k,
                                             int subpixel, double *flow, double *cost, double *curv);
+/* gqmap_block_match_window with H ranked hypotheses per pixel ("Ranked windows"
+ * of csrc/gqmap_blockmatch.h).  win: int32, M x N x 4 x H, rank slowest, slice j
+ * laid out as gqmap_block_match_window's win: box j of every pixel.  H in [1,4],
+ * sep in [1,65].  Rank j is the pick of gqmap_block_match_window over the
+ * displacements of ITS box j that are at least sep away (larger of the row and
+ * column distance) from the pick of every earlier rank that has one.  A rank
+ * whose box is empty, or in which nothing is allowed, is missing: flow NaN, cost
+ * +Inf, curv 0; it excludes nothing, and later ranks go on.
+ * flow (M x N x 2 x H), cost (M x N x H, may be NULL), curv (M x N x 2 x H, may be
+ * NULL): slice j signed and laid out as gqmap_block_match_window's.  subpixel
+ * != 0: the parabola per rank and axis, refinable only when both neighbours lie
+ * inside that rank's own box; the neighbours' costs are the plain filtered costs
+ * whether or not the separation would allow them.
+ * H = 1 is gqmap_block_match_window; rank 0 is gqmap_block_match_window on box 0
+ * whatever H and sep; with all H boxes [-U, U] x [-V, V] the results are
+ * gqmap_block_match_multi's (subpixel = 0) and gqmap_block_match_refine's
+ * (subpixel != 0) at the same H and sep, all bit for bit.
+ * One kernel for all ranks; elapsed_ms (may be NULL) as above. */
+gqmap_status gqmap_block_match_window_multi(const double *A, const double *B, const int *win, int M,
+                                            int N, int ft, double sigma, int H, int sep,
+                                            int subpixel, double *flow, double *cost, double *curv,
+                                            double *elapsed_ms, int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_block_match_window_multi_host(const double *A, const double *B, const int *win,
+                                                 int M, int N, int ft, double sigma, int H, int sep,
+                                                 int subpixel, double *flow, double *cost,
+                                                 double *curv);
+/* gqmap_block_match_pyramid with H ranked hypotheses per pixel ("Ranked coarse to
+ * fine").  At the coarsest level all H boxes are [-Uc, Uc] x [-Vc, Vc]; going
+ * down, box j of a fine pixel is the window rule of gqmap_block_match_pyramid
+ * over the coarse level's rank-j picks (a coarse pixel that misses rank j adds
+ * nothing).  Every level runs gqmap_block_match_window_multi with the same H and
+ * sep; only level 0 applies subpixel, and the outputs are level 0's, shaped as
+ * gqmap_block_match_window_multi's.  H = 1, and rank 0 at any H and sep, are
+ * gqmap_block_match_pyramid; levels = 1 is gqmap_block_match_multi /
+ * gqmap_block_match_refine, bit for bit.  Arguments as gqmap_block_match_pyramid's
+ * and H, sep as above.  Frames, picks (H x 2 planes per level) and windows of all
+ * levels stay on the device; elapsed_ms covers all kernels of the call. */
+gqmap_status gqmap_block_match_pyramid_multi(const double *A, const double *B, int M, int N, int U,
+                                             int V, int ft, double sigma, int levels, int r, int k,
+                                             int H, int sep, int subpixel, double *flow,
+                                             double *cost, double *curv, double *elapsed_ms,
+                                             int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_block_match_pyramid_multi_host(const double *A, const double *B, int M, int N,
+                                                  int U, int V, int ft, double sigma, int levels,
+                                                  int r, int k, int H, int sep, int subpixel,
+                                                  double *flow, double *cost, double *curv);
 /* ceil(U / 2^c) 2^c + r (2^c - 1), c = levels - 1: the largest displacement along
  * an axis that gqmap_block_match_pyramid can return (-1: argument out of range) */
 int gqmap_block_match_reach(int U, int levels, int r);
