@@ -237,22 +237,6 @@ static hipError_t bm_launch(const double *dA, const double *dB, int M, int N, in
 using namespace gq;
 
 namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
 // gqmap_block_match (H = 0), gqmap_block_match_multi (H >= 1) and gqmap_block_match_refine (H >= 1, refine; curv
 // may be null) behind one body; who names the caller in errors
 static gqmap_status bm_device(const char *who, const double *A, const double *B, int M, int N, int U, int V, int ft,

@@ -116,15 +116,6 @@ __global__ __launch_bounds__(FC_THREADS) void k_flow_fill(const double *__restri
 using namespace gq;
 
 namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    double *d() const { return (double *)p; }
-    unsigned char *b() const { return (unsigned char *)p; }
-};
 // kernel time on the null stream (off: no events, no waits)
 struct Stopwatch {
     hipEvent_t a = nullptr, b = nullptr;

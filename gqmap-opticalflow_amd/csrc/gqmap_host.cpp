@@ -402,106 +402,20 @@ gqmap_status gqmap_block_match_refine_host(const double *A, const double *B, int
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// Per-pixel windows and the coarse-to-fine scheme, host models ("Per-pixel
-// windows" and "Coarse to fine" of gqmap_blockmatch.h).  Tile by tile, as the
-// kernel: a displacement is evaluated over a 32 x 32 tile when one of the
-// tile's pixels has it in its box, so the work follows the windows and not
-// their union over the frame.  The pick rule knows no scan order, so the
-// tiling shows in no result.
+// Per-pixel windows and the coarse-to-fine scheme, plain and ranked, host
+// models ("Per-pixel windows", "Coarse to fine", "Ranked windows" and "Ranked
+// coarse to fine" of gqmap_blockmatch.h).  Tile by tile, as the kernel: a
+// displacement is evaluated over a 32 x 32 tile when one of the tile's pixels
+// has it in its box, so the work follows the windows and not their union over
+// the frame.  The pick rule knows no scan order, so the tiling shows in no
+// result.  The plain entry points are the ranked ones at H = 1: no earlier
+// rank excludes anything and every rank offset is zero.
 // ---------------------------------------------------------------------------
 namespace {
 
-// one level: win (M x N x 4) or, when null, the box cbox at every pixel.  flow, cost, curv and pick (planes du, dv;
-// GQ_BM_NOPICK without a pick) may each be null.
-void bm_window_level(const double *A, const double *B, int M, int N, const int *win, const int cbox[4], int ft,
-                     const gq::BmFilter &f, bool subpixel, double *flow, double *cost, double *curv, int *pick)
-{
-    constexpr int TM = 32, TN = 32;
-    const int AH = TM + 2 * ft, AW = TN + 2 * ft;
-    const size_t MN = (size_t)M * N;
-    std::vector<double> As((size_t)AH * AW), bcol(AH), T((size_t)TM * AW), best(TM * TN);
-    std::vector<int> box(4 * TM * TN), key(TM * TN);
-    std::vector<gq::BmNear> nbr(TM * TN);
-    for (int n0 = 0; n0 < N; n0 += TN)
-        for (int m0 = 0; m0 < M; m0 += TM) {
-            const int th = std::min(TM, M - m0), tw = std::min(TN, N - n0);
-            int un[4] = {GQ_BM_NOPICK, -GQ_BM_NOPICK, GQ_BM_NOPICK, -GQ_BM_NOPICK};
-            for (int j = 0; j < tw; ++j)
-                for (int i = 0; i < th; ++i) {
-                    int *b = &box[4 * (i + TM * j)];
-                    for (int q = 0; q < 4; ++q) b[q] = win ? win[(m0 + i) + (size_t)M * (n0 + j) + MN * q] : cbox[q];
-                    best[i + TM * j] = INFINITY;
-                    key[i + TM * j] = GQ_BM_NOPICK;
-                    gq::bm_near_clear(nbr[i + TM * j]);
-                    if (b[0] > b[1] || b[2] > b[3]) continue;
-                    un[0] = std::min(un[0], b[0]);
-                    un[1] = std::max(un[1], b[1]);
-                    un[2] = std::min(un[2], b[2]);
-                    un[3] = std::max(un[3], b[3]);
-                }
-            for (int c = 0; c < AW; ++c)
-                for (int i = 0; i < AH; ++i) {
-                    const int gm = m0 - ft + i, gn = n0 - ft + c;
-                    As[i + (size_t)AH * c] = gm >= 0 && gm < M && gn >= 0 && gn < N ? A[gm + (size_t)M * gn] : 0.0;
-                }
-            for (int pass = 0; pass < (subpixel ? 2 : 1); ++pass)
-                for (int dv = un[2]; dv <= un[3]; ++dv)
-                    for (int du = un[0]; du <= un[1]; ++du) {
-                        bool any = false;
-                        for (int j = 0; j < tw && !any; ++j)
-                            for (int i = 0; i < th && !any; ++i) {
-                                const int o = i + TM * j;
-                                any = pass == 0 ? gq::bm_in_box(&box[4 * o], du, dv)
-                                                : gq::bm_near_wanted(&box[4 * o], du, dv, key[o]);
-                            }
-                        if (!any) continue;
-                        for (int c = 0; c < tw + 2 * ft; ++c) {
-                            const int gn = n0 - ft + c;
-                            for (int i = 0; i < AH; ++i) {
-                                const int bm = m0 - ft + i + du, bn = gn + dv;
-                                bcol[i] = bm >= 0 && bm < M && bn >= 0 && bn < N ? B[bm + (size_t)M * bn] : 0.0;
-                            }
-                            for (int i = 0; i < th; ++i)
-                                T[i + (size_t)TM * c] = gq::bm_rows(&As[i + (size_t)AH * c], &bcol[i], ft, f, m0 + i - ft,
-                                                                    M, gn >= 0 && gn < N);
-                        }
-                        for (int j = 0; j < tw; ++j)
-                            for (int i = 0; i < th; ++i) {
-                                const int o = i + TM * j;
-                                const double c = gq::bm_cols(&T[i + (size_t)TM * j], TM, ft, f);
-                                if (pass == 0)
-                                    gq::bm_keep_window(gq::bm_in_box(&box[4 * o], du, dv), c, du, dv, best[o], key[o]);
-                                else
-                                    gq::bm_capture_window(du, dv, key[o], c, nbr[o]);
-                            }
-                    }
-            for (int j = 0; j < tw; ++j)
-                for (int i = 0; i < th; ++i) {
-                    const int o = i + TM * j;
-                    const size_t g = (m0 + i) + (size_t)M * (n0 + j);
-                    double out[4];
-                    gq::bm_refined_window(key[o], best[o], nbr[o], &box[4 * o], subpixel, out);
-                    if (flow) {
-                        flow[g] = out[0];
-                        flow[g + MN] = out[1];
-                    }
-                    if (cost) cost[g] = best[o];
-                    if (curv) {
-                        curv[g] = out[2];
-                        curv[g + MN] = out[3];
-                    }
-                    if (pick) {
-                        const bool found = key[o] != GQ_BM_NOPICK;
-                        pick[g] = found ? gq::bm_key_du(key[o]) : GQ_BM_NOPICK;
-                        pick[g + MN] = found ? gq::bm_key_dv(key[o]) : GQ_BM_NOPICK;
-                    }
-                }
-        }
-}
-
 // one level of "Ranked windows": win (M x N x 4 x H) or, when null, the box cbox at every pixel and rank.  flow, curv
-// (M x N x 2 x H), cost (M x N x H) and pick (per rank the planes du, dv) may each be null.  Tile by tile as
-// bm_window_level, the rank loop inside the tile: the A tile is staged once, only the keys survive a rank.
+// (M x N x 2 x H), cost (M x N x H) and pick (per rank the planes du, dv; GQ_BM_NOPICK without a pick) may each be
+// null.  The rank loop is inside the tile: the A tile is staged once, only the keys survive a rank.
 void bm_ranked_level(const double *A, const double *B, int M, int N, const int *win, const int cbox[4], int ft,
                      const gq::BmFilter &f, int H, int sep, bool subpixel, double *flow, double *cost, double *curv,
                      int *pick)
@@ -600,6 +514,51 @@ void bm_ranked_level(const double *A, const double *B, int M, int N, const int *
         }
 }
 
+// "Coarse to fine" and "Ranked coarse to fine": the frames halved up to level levels - 1, the boxes of a level from
+// the H pick-plane pairs of the level above, level 0's outputs returned
+void bm_pyramid_levels(const double *A, const double *B, int M, int N, int U, int V, int ft, double sigma, int levels,
+                       int r, int k, int H, int sep, bool subpixel, double *flow, double *cost, double *curv)
+{
+    const gq::BmFilter f = gq::bm_filter(ft, sigma);
+    const int c = levels - 1;
+    std::vector<std::vector<double>> As(levels), Bs(levels);
+    std::vector<int> Ms(levels, M), Ns(levels, N);
+    for (int l = 1; l < levels; ++l) {
+        const int Mp = Ms[l - 1], Np = Ns[l - 1];
+        Ms[l] = (Mp + 1) / 2, Ns[l] = (Np + 1) / 2;
+        As[l].resize((size_t)Ms[l] * Ns[l]);
+        Bs[l].resize((size_t)Ms[l] * Ns[l]);
+        for (int j = 0; j < Ns[l]; ++j)
+            for (int i = 0; i < Ms[l]; ++i) {
+                As[l][i + (size_t)Ms[l] * j] = gq::bm_half(l == 1 ? A : As[l - 1].data(), Mp, Np, i, j);
+                Bs[l][i + (size_t)Ms[l] * j] = gq::bm_half(l == 1 ? B : Bs[l - 1].data(), Mp, Np, i, j);
+            }
+    }
+    const int Uc = gq::bm_ceil_shift(U, c), Vc = gq::bm_ceil_shift(V, c);
+    const int cbox[4] = {-Uc, Uc, -Vc, Vc};
+    std::vector<int> pick, win;  // H pick-plane pairs of the level above, H boxes of this one
+    for (int l = c; l >= 0; --l) {
+        const double *a = l == 0 ? A : As[l].data(), *b = l == 0 ? B : Bs[l].data();
+        const size_t mn = (size_t)Ms[l] * Ns[l];
+        if (l < c) {
+            const size_t mnc = (size_t)Ms[l + 1] * Ns[l + 1];
+            win.resize(4 * mn * H);
+            for (int j = 0; j < H; ++j)
+                for (int n = 0; n < Ns[l]; ++n)
+                    for (int m = 0; m < Ms[l]; ++m) {
+                        int box[4];
+                        gq::bm_window_up(pick.data() + 2 * mnc * j, Ms[l + 1], Ns[l + 1], m, n, r, k, box);
+                        for (int q = 0; q < 4; ++q) win[m + (size_t)Ms[l] * n + mn * q + 4 * mn * j] = box[q];
+                    }
+        }
+        std::vector<int> next(l > 0 ? 2 * mn * H : 0);
+        bm_ranked_level(a, b, Ms[l], Ns[l], l < c ? win.data() : nullptr, cbox, ft, f, H, sep, l == 0 && subpixel,
+                        l == 0 ? flow : nullptr, l == 0 ? cost : nullptr, l == 0 ? curv : nullptr,
+                        l > 0 ? next.data() : nullptr);
+        pick.swap(next);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -636,44 +595,7 @@ gqmap_status gqmap_block_match_pyramid_multi_host(const double *A, const double 
              N, U, V, ft, sigma, levels, r, k);
     bad = gq::bm_bad_multi(H, sep);
     GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG, "gqmap_block_match_pyramid_multi_host: %s (H=%d sep=%d)", bad, H, sep);
-    const gq::BmFilter f = gq::bm_filter(ft, sigma);
-    const int c = levels - 1;
-    std::vector<std::vector<double>> As(levels), Bs(levels);
-    std::vector<int> Ms(levels, M), Ns(levels, N);
-    for (int l = 1; l < levels; ++l) {
-        const int Mp = Ms[l - 1], Np = Ns[l - 1];
-        Ms[l] = (Mp + 1) / 2, Ns[l] = (Np + 1) / 2;
-        As[l].resize((size_t)Ms[l] * Ns[l]);
-        Bs[l].resize((size_t)Ms[l] * Ns[l]);
-        for (int j = 0; j < Ns[l]; ++j)
-            for (int i = 0; i < Ms[l]; ++i) {
-                As[l][i + (size_t)Ms[l] * j] = gq::bm_half(l == 1 ? A : As[l - 1].data(), Mp, Np, i, j);
-                Bs[l][i + (size_t)Ms[l] * j] = gq::bm_half(l == 1 ? B : Bs[l - 1].data(), Mp, Np, i, j);
-            }
-    }
-    const int Uc = gq::bm_ceil_shift(U, c), Vc = gq::bm_ceil_shift(V, c);
-    const int cbox[4] = {-Uc, Uc, -Vc, Vc};
-    std::vector<int> pick, win;  // H pick-plane pairs of the level above, H boxes of this one
-    for (int l = c; l >= 0; --l) {
-        const double *a = l == 0 ? A : As[l].data(), *b = l == 0 ? B : Bs[l].data();
-        const size_t mn = (size_t)Ms[l] * Ns[l];
-        if (l < c) {
-            const size_t mnc = (size_t)Ms[l + 1] * Ns[l + 1];
-            win.resize(4 * mn * H);
-            for (int j = 0; j < H; ++j)
-                for (int n = 0; n < Ns[l]; ++n)
-                    for (int m = 0; m < Ms[l]; ++m) {
-                        int box[4];
-                        gq::bm_window_up(pick.data() + 2 * mnc * j, Ms[l + 1], Ns[l + 1], m, n, r, k, box);
-                        for (int q = 0; q < 4; ++q) win[m + (size_t)Ms[l] * n + mn * q + 4 * mn * j] = box[q];
-                    }
-        }
-        std::vector<int> next(l > 0 ? 2 * mn * H : 0);
-        bm_ranked_level(a, b, Ms[l], Ns[l], l < c ? win.data() : nullptr, cbox, ft, f, H, sep, l == 0 && subpixel != 0,
-                        l == 0 ? flow : nullptr, l == 0 ? cost : nullptr, l == 0 ? curv : nullptr,
-                        l > 0 ? next.data() : nullptr);
-        pick.swap(next);
-    }
+    bm_pyramid_levels(A, B, M, N, U, V, ft, sigma, levels, r, k, H, sep, subpixel != 0, flow, cost, curv);
     return GQMAP_OK;
 }
 
@@ -693,7 +615,8 @@ gqmap_status gqmap_block_match_window_host(const double *A, const double *B, con
              sigma);
     GQ_CHECK(!gq::bm_bad_bounds(win, M, N), GQMAP_ERR_INVALID_ARG,
              "gqmap_block_match_window_host: a window bound outside [-%d,%d]", GQ_BM_DMAX, GQ_BM_DMAX);
-    bm_window_level(A, B, M, N, win, nullptr, ft, gq::bm_filter(ft, sigma), subpixel != 0, flow, cost, curv, nullptr);
+    bm_ranked_level(A, B, M, N, win, nullptr, ft, gq::bm_filter(ft, sigma), 1, 0, subpixel != 0, flow, cost, curv,
+                    nullptr);
     return GQMAP_OK;
 }
 
@@ -707,42 +630,7 @@ gqmap_status gqmap_block_match_pyramid_host(const double *A, const double *B, in
     GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG,
              "gqmap_block_match_pyramid_host: %s (M=%d N=%d U=%d V=%d ft=%d sigma=%g levels=%d r=%d k=%d)", bad, M, N, U,
              V, ft, sigma, levels, r, k);
-    const gq::BmFilter f = gq::bm_filter(ft, sigma);
-    const int c = levels - 1;
-    std::vector<std::vector<double>> As(levels), Bs(levels);
-    std::vector<int> Ms(levels, M), Ns(levels, N);
-    for (int l = 1; l < levels; ++l) {
-        const int Mp = Ms[l - 1], Np = Ns[l - 1];
-        Ms[l] = (Mp + 1) / 2, Ns[l] = (Np + 1) / 2;
-        As[l].resize((size_t)Ms[l] * Ns[l]);
-        Bs[l].resize((size_t)Ms[l] * Ns[l]);
-        for (int j = 0; j < Ns[l]; ++j)
-            for (int i = 0; i < Ms[l]; ++i) {
-                As[l][i + (size_t)Ms[l] * j] = gq::bm_half(l == 1 ? A : As[l - 1].data(), Mp, Np, i, j);
-                Bs[l][i + (size_t)Ms[l] * j] = gq::bm_half(l == 1 ? B : Bs[l - 1].data(), Mp, Np, i, j);
-            }
-    }
-    const int Uc = gq::bm_ceil_shift(U, c), Vc = gq::bm_ceil_shift(V, c);
-    const int cbox[4] = {-Uc, Uc, -Vc, Vc};
-    std::vector<int> pick, win;
-    for (int l = c; l >= 0; --l) {
-        const double *a = l == 0 ? A : As[l].data(), *b = l == 0 ? B : Bs[l].data();
-        const size_t mn = (size_t)Ms[l] * Ns[l];
-        if (l < c) {
-            win.resize(4 * mn);
-            for (int n = 0; n < Ns[l]; ++n)
-                for (int m = 0; m < Ms[l]; ++m) {
-                    int box[4];
-                    gq::bm_window_up(pick.data(), Ms[l + 1], Ns[l + 1], m, n, r, k, box);
-                    for (int q = 0; q < 4; ++q) win[m + (size_t)Ms[l] * n + mn * q] = box[q];
-                }
-        }
-        std::vector<int> next(l > 0 ? 2 * mn : 0);
-        bm_window_level(a, b, Ms[l], Ns[l], l < c ? win.data() : nullptr, cbox, ft, f, l == 0 && subpixel != 0,
-                        l == 0 ? flow : nullptr, l == 0 ? cost : nullptr, l == 0 ? curv : nullptr,
-                        l > 0 ? next.data() : nullptr);
-        pick.swap(next);
-    }
+    bm_pyramid_levels(A, B, M, N, U, V, ft, sigma, levels, r, k, 1, 0, subpixel != 0, flow, cost, curv);
     return GQMAP_OK;
 }
 

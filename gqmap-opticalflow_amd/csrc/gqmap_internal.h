@@ -62,6 +62,33 @@ struct DeviceGuard {
     }
 };
 
+// A device allocation freed on scope exit (movable, so that a std::vector can hold one per level).
+struct DevBuf {
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    ~DevBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    double *d() const { return (double *)p; }
+    unsigned char *b() const { return (unsigned char *)p; }
+};
+
+// The event pair around a call's kernels (elapsed_ms), and further events for counting runs; destroyed on scope exit.
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    std::vector<hipEvent_t> more;
+    ~Events()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        for (hipEvent_t e : more)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
 // Host fp64 getVV (gqmap_gpu_mixture.m:191-208), independent of the oracle.
 void build_padded(const double *I2, int M, int N, double *VV);
 // Gauss-Hermite by Newton iteration on the orthonormal Hermite recurrence.

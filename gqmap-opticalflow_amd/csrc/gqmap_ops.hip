@@ -264,16 +264,6 @@ static void make_wheel(unsigned char w[55][3])
 
 using namespace gq;
 
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
-}  // namespace
-
 extern "C" {
 
 gqmap_status gqmap_projsplx(const double *Y, double *X, int n, int ncols, int device)

@@ -245,14 +245,6 @@ static hipError_t rof_launch_fused(const double *x, const double *p1in, const do
 using namespace gq;
 
 namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    double *d() const { return (double *)p; }
-};
 // kernel time over several stretches of the null stream (off: no events, no waits)
 struct Stopwatch {
     hipEvent_t a = nullptr, b = nullptr;

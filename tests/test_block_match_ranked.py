@@ -3,15 +3,12 @@ matcher, host models (gqmap_block_match_window_multi_host,
 gqmap_block_match_pyramid_multi_host) against the numpy restatement of
 tests/_blockmatch_ranked_np.py, bit for bit; the three identities of the header
 against the existing host models; missing ranks; argument errors;
-block_match_init(pyr_ranked=True); the quality of three ranks on whole frames;
-the kernels' code object.  No device."""
+block_match_init(pyr_ranked=True); the quality of three ranks on whole frames.
+The kernels' code object is checked in tests/test_block_match_window.py.  No
+device."""
 import ctypes as C
 import functools
 import itertools
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -427,54 +424,3 @@ def test_urban3_three_ranks_beat_rank_0():
     """480 x 640, (20, 20, 3, 1.7), three levels.  Measured: rank 0 3.89960, best of 3 ranks 2.53447."""
     a, b = best_of_ranks("Urban3", (20, 20, 3, 1.7), 3)
     assert b < a
-
-
-# ---- the kernels' listing ----------------------------------------------------------------------
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gqmap-opticalflow_amd", "libgqmap.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-# the VGPR count of the built instantiation falls under this occupancy step (128: four workgroups of 256 lanes per
-# CU, 168: three, 256: two), by NPT and integer / sub-pixel
-VGPR_STEP = {"ILi1ELb0E": 128, "ILi2ELb0E": 128, "ILi4ELb0E": 168, "ILi1ELb1E": 128, "ILi2ELb1E": 128, "ILi4ELb1E": 168}
-
-
-@pytest.mark.skipif(not os.path.exists(LIB) or not shutil.which(f"{LLVM}/llvm-readelf"),
-                    reason="library or ROCm LLVM tools absent")
-def test_ranked_kernels_have_no_scratch_and_bounded_registers(tmp_path):
-    """In the manner of tests/test_block_match_window.py: the gfx950 code object's
-    metadata.  Six instantiations of k_block_match_ranked (tile widths 8, 16, 32;
-    integer and sub-pixel), none with scratch or spills to memory; each stays
-    under the occupancy step its built register count falls under.  The earlier
-    ranks' keys (three ints per output) and the rank loop cost registers beside
-    k_block_match_window: at 32 columns both modes sit in the 168 step, where
-    the tile's LDS allows no more than three workgroups per CU anyway."""
-    tmp = str(tmp_path)
-    fat = os.path.join(tmp, "fatbin.bin")
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", LIB, os.path.join(tmp, "x.so")],
-                   check=True, capture_output=True)
-    with open(fat, "rb") as fh:
-        blob = fh.read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)]
-    seen = {}
-    for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(blob)])):
-        part, co = os.path.join(tmp, f"part{i}.bin"), os.path.join(tmp, f"co{i}.elf")
-        with open(part, "wb") as fh:
-            fh.write(blob[a:b])
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-        for block in re.split(r"\n  - ", notes):
-            name = re.search(r"\n\s*\.name:\s+(\S+)", "\n" + block)
-            if name and "k_block_match_ranked" in name.group(1):
-                seen[name.group(1)] = {key: int(re.search(rf"\.{key}:\s+(\d+)", block).group(1)) for key in
-                                       ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count",
-                                        "vgpr_count")}
-    assert len(seen) == 6, sorted(seen)
-    for name, v in seen.items():
-        step = [s for tag, s in VGPR_STEP.items() if tag in name]
-        assert len(step) == 1, name
-        print(name, v)
-        assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0, name
-        assert v["vgpr_count"] <= step[0], (name, v)
-        assert v["group_segment_fixed_size"] <= 1024, (name, v)

@@ -5,16 +5,13 @@ numpy restatement of tests/_blockmatch_window_np.py, bit for bit; the anchor
 the full search on whole frames; block_match_init(levels=).  No device."""
 import ctypes as C
 import functools
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import _blockmatch_np as R
 from tests import _blockmatch_window_np as W
+from tests import _codeobj
 
 NAN_BITS = 0x7FF8000000000000
 CROP_97 = "97x130"
@@ -339,47 +336,42 @@ def test_levels_2_with_several_hypotheses_raises():
 
 # ---- the kernels' listing ------------------------------------------------------------------------
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gqmap-opticalflow_amd", "libgqmap.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
+# the occupancy step (128 VGPRs: four workgroups of 256 lanes per CU, 168: three) of each instantiation of
+# k_block_match_window<NPT, REFINE, RANKED>, by the template arguments in the mangled name
+VGPR_STEP = {
+    "ILi1ELb0ELb0E": 128, "ILi2ELb0ELb0E": 128, "ILi4ELb0ELb0E": 128,  # plain, integer
+    "ILi1ELb1ELb0E": 128, "ILi2ELb1ELb0E": 128, "ILi4ELb1ELb0E": 168,  # plain, sub-pixel
+    "ILi1ELb0ELb1E": 128, "ILi2ELb0ELb1E": 128, "ILi4ELb0ELb1E": 168,  # ranked, integer
+    "ILi1ELb1ELb1E": 128, "ILi2ELb1ELb1E": 128, "ILi4ELb1ELb1E": 168,  # ranked, sub-pixel
+}
 
 
-@pytest.mark.skipif(not os.path.exists(LIB) or not shutil.which(f"{LLVM}/llvm-readelf"),
-                    reason="library or ROCm LLVM tools absent")
-def test_window_kernels_have_no_scratch_and_bounded_registers(tmp_path):
-    """In the manner of tests/test_flow_check.py: the gfx950 code object's
-    metadata.  Six instantiations of k_block_match_window (tile widths 8, 16, 32;
-    integer and sub-pixel), none with scratch or spills.  The integer kernels
-    stay within the 128 VGPRs that allow four workgroups per CU; the sub-pixel
-    kernel at 32 columns carries four neighbour costs per output on top and may
-    use up to 168 (three workgroups per CU).  Static LDS (the union box and the
+@pytest.mark.skipif(not _codeobj.available(), reason="library or ROCm LLVM tools absent")
+def test_window_kernels_have_no_scratch_and_bounded_registers():
+    """The gfx950 code object's metadata (tests/_codeobj.py).  Twelve
+    instantiations of k_block_match_window (tile widths 8, 16, 32; integer and
+    sub-pixel; plain and ranked) beside k_bm_half and k_bm_window_up, none with
+    scratch or spills, and no separate ranked kernel.  The plain integer kernels
+    stay within the 128 VGPRs that allow four workgroups per CU; the plain
+    sub-pixel kernel at 32 columns carries four neighbour costs per output on
+    top and may use up to 168 (three workgroups per CU).  The earlier ranks'
+    keys (three ints per output) and the rank loop cost registers: at 32 columns
+    both ranked modes sit in the 168 step, where the tile's LDS allows no more
+    than three workgroups per CU anyway.  Static LDS (the union box and the
     vote) stays small beside the dynamic tile."""
-    tmp = str(tmp_path)
-    fat = os.path.join(tmp, "fatbin.bin")
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", LIB, os.path.join(tmp, "x.so")],
-                   check=True, capture_output=True)
-    with open(fat, "rb") as fh:
-        blob = fh.read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)]
-    seen = {}
-    for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(blob)])):
-        part, co = os.path.join(tmp, f"part{i}.bin"), os.path.join(tmp, f"co{i}.elf")
-        with open(part, "wb") as fh:
-            fh.write(blob[a:b])
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-        for block in re.split(r"\n  - ", notes):
-            name = re.search(r"\n\s*\.name:\s+(\S+)", "\n" + block)
-            if name and re.search(r"k_block_match_window|k_bm_half|k_bm_window_up", name.group(1)):
-                seen[name.group(1)] = {key: int(re.search(rf"\.{key}:\s+(\d+)", block).group(1)) for key in
-                                       ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count",
-                                        "vgpr_count")}
+    every = _codeobj.kernels()
+    # the family has one tile kernel (the full search's k_block_match<...> mangles without the underscore)
+    assert not [k for k in every if "k_block_match_" in k and "k_block_match_window" not in k]
+    seen = {k: v for k, v in every.items() if "k_block_match_window" in k or "k_bm_half" in k or "k_bm_window_up" in k}
     window = {k: v for k, v in seen.items() if "k_block_match_window" in k}
-    assert len(window) == 6 and len(seen) == 8, sorted(seen)
+    assert len(window) == 12 and len(seen) == 14, sorted(seen)
     for name, v in seen.items():
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0, name
+    steps = dict(VGPR_STEP)
     for name, v in window.items():
-        refine32 = "ILi4ELb1E" in name
-        assert v["vgpr_count"] <= (168 if refine32 else 128), (name, v)
+        tag = [t for t in steps if t in name]
+        assert len(tag) == 1, name
+        print(name, v)
+        assert v["vgpr_count"] <= steps.pop(tag[0]), (name, v)
         assert v["group_segment_fixed_size"] <= 1024, (name, v)
+    assert not steps, sorted(steps)

@@ -5,15 +5,13 @@ closed forms of both, argument errors, and block_match_init(consistency=,
 fill=) on crops and on the whole RubberWhale pair.  The kernels against the
 host models: tests/test_gpu_flow_check.py."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import _blockmatch_np as R
+from tests import _codeobj
 from tests import _flowcheck_np as F
 from tests._flowcheck_np import bits
 
@@ -445,40 +443,16 @@ def test_whole_frame_check_separates_and_the_fill_improves_the_start():
 
 # ---- the kernels' listing ------------------------------------------------------------------
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gqmap-opticalflow_amd", "libgqmap.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
 CU_LDS = 160 * 1024
 
 
-@pytest.mark.skipif(not os.path.exists(LIB) or not shutil.which(f"{LLVM}/llvm-readelf"),
-                    reason="library or ROCm LLVM tools absent")
-def test_kernels_have_no_scratch_and_the_fill_fits_the_lds(tmp_path):
-    """In the manner of tests/test_occupancy.py: the gfx950 code object's
-    metadata.  The fill's tile is dynamic LDS, 8 W (3 W + 32) bytes with
+@pytest.mark.skipif(not _codeobj.available(), reason="library or ROCm LLVM tools absent")
+def test_kernels_have_no_scratch_and_the_fill_fits_the_lds():
+    """The gfx950 code object's metadata (tests/_codeobj.py).  The fill's tile is dynamic LDS, 8 W (3 W + 32) bytes with
     W = 32 + 2r, on top of what the kernel holds statically."""
     from gqmap_opticalflow_amd import _lib
-    tmp = str(tmp_path)
-    fat = os.path.join(tmp, "fatbin.bin")
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", LIB, os.path.join(tmp, "x.so")],
-                   check=True, capture_output=True)
-    # one bundle per translation unit, each behind the bundler's magic string
-    with open(fat, "rb") as fh:
-        blob = fh.read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)]
-    seen = {}
-    for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(blob)])):
-        part, co = os.path.join(tmp, f"part{i}.bin"), os.path.join(tmp, f"co{i}.elf")
-        with open(part, "wb") as fh:
-            fh.write(blob[a:b])
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-        for block in re.split(r"\n  - ", notes):
-            name = re.search(r"\n\s*\.name:\s+(\S+)", "\n" + block)
-            if name and re.search(r"k_flow_(check|fill)", name.group(1)):
-                seen[name.group(1)] = tuple(int(re.search(rf"\.{key}:\s+(\d+)", block).group(1)) for key in
-                                            ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count"))
+    seen = {k: (v["private_segment_fixed_size"], v["group_segment_fixed_size"], v["vgpr_spill_count"])
+            for k, v in _codeobj.kernels().items() if re.search(r"k_flow_(check|fill)", k)}
     check = [v for k, v in seen.items() if "k_flow_check" in k]
     fill = [v for k, v in seen.items() if "k_flow_fill" in k]
     assert len(check) == 1 and len(fill) == 1, sorted(seen)

@@ -1,5 +1,5 @@
 """gqmap_block_match_window_multi and gqmap_block_match_pyramid_multi (the HIP
-kernel k_block_match_ranked) against their host models: one header
+kernel k_block_match_window, RANKED) against their host models: one header
 (csrc/gqmap_blockmatch.h) behind both, so flow, cost and curvature of every rank
 agree BIT FOR BIT, NaN patterns included, whatever the tile width and the chunk
 extent; the host models are checked against numpy in

@@ -4,16 +4,10 @@ sit on register thresholds (MI355X: <= 128 VGPRs -> 4 waves per SIMD, <= 168
 VGPRs on the C2 fp64 kernel (168 -> 170, 3 -> 2 waves) made it 9% slower
 (profiles/r04_banded_pipeline.txt).  Reads .vgpr_count / .agpr_count from
 the gfx950 code object's metadata in gqmap-opticalflow_amd/libgqmap.so."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gqmap-opticalflow_amd", "libgqmap.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
+from tests import _codeobj
+from tests._codeobj import LIB, LLVM  # tests/test_tap_lut.py reads them here
 
 # kernel (mangled) -> max VGPRs (agpr 0): C2 fp64 (3 waves), C2 fp32 (4), C3's
 # full level (3), its 240x320 level and C4 (2, no accumulation registers), the
@@ -69,28 +63,13 @@ SCRATCH_MAX = {
 }
 
 
-def _kernel_registers(tmp):
-    fat = os.path.join(tmp, "fatbin.bin")
-    co = os.path.join(tmp, "co.elf")
-    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", LIB, os.path.join(tmp, "x.so")],
-                   check=True, capture_output=True)
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
-                           text=True).stdout
-    regs = {}
-    for block in re.split(r"\n  - ", notes):
-        name = re.search(r"\n\s*\.name:\s+(\S+)", "\n" + block)
-        v = re.search(r"\.vgpr_count:\s+(\d+)", block)
-        a = re.search(r"\.agpr_count:\s+(\d+)", block)
-        sc = re.search(r"\.private_segment_fixed_size:\s+(\d+)", block)
-        if name and v:
-            regs[name.group(1)] = (int(v.group(1)), int(a.group(1)) if a else 0, int(sc.group(1)) if sc else 0)
-    return regs
+def _kernel_registers(tmp=None):
+    """name -> (VGPRs, AGPRs, scratch bytes)"""
+    return {name: (v["vgpr_count"], v["agpr_count"], v["private_segment_fixed_size"])
+            for name, v in _codeobj.kernels(LIB).items()}
 
 
-@pytest.mark.skipif(not os.path.exists(LIB) or not shutil.which(f"{LLVM}/llvm-readelf"),
-                    reason="library or ROCm LLVM tools absent")
+@pytest.mark.skipif(not _codeobj.available(), reason="library or ROCm LLVM tools absent")
 def test_headline_kernels_keep_their_waves(tmp_path):
     regs = _kernel_registers(str(tmp_path))
     for name, limit in LIMITS.items():
