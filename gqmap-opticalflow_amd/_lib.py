@@ -22,6 +22,7 @@ ARITH_FAST, ARITH_LITERAL = 0, 1  # gqmap_options.arith (ABI 2)
 ABI_VERSION = 2
 SPLIT_ROLE = -1  # GQMAP_SPLIT_ROLE: options["split"] for the role-split kernel shape (Q = 1 arithmetic)
 LMAX, KMAX = 8, 16
+SCATTER_REFERENCE, SCATTER_ADJOINT = 0, 1  # GQMAP_SCATTER_*
 
 # Every entry point declared in include/gqmap.h (checked by tests/test_abi.py).
 EXPORTS = (
@@ -44,6 +45,7 @@ EXPORTS = (
     "gqmap_block_match_pyramid_host", "gqmap_block_match_reach",
     "gqmap_block_match_window_multi", "gqmap_block_match_window_multi_host", "gqmap_block_match_pyramid_multi",
     "gqmap_block_match_pyramid_multi_host",
+    "gqmap_flow_denoise", "gqmap_flow_denoise_device", "gqmap_flow_denoise_host",
 )
 CTF_MAX_LEVELS = 8
 
@@ -203,6 +205,12 @@ def load():
                                     P(C.c_int), C.c_int]),
         "gqmap_cpu_run_device": (C.c_int, [P(GqmapCpuOptions), vp, C.c_int, C.c_int, vp, C.c_uint64, vp, vp, vp,
                                            vp, P(C.c_int), C.c_int]),
+        "gqmap_flow_denoise": (C.c_int, [P(GqmapCpuOptions), _D, _D, _D, C.c_int, C.c_int, _D, C.c_uint64, C.c_int, _D,
+                                         _D, _D, _D, P(C.c_int), C.c_int]),
+        "gqmap_flow_denoise_device": (C.c_int, [P(GqmapCpuOptions), vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64,
+                                                C.c_int, vp, vp, vp, vp, P(C.c_int), C.c_int]),
+        "gqmap_flow_denoise_host": (C.c_int, [P(GqmapCpuOptions), _D, _D, _D, C.c_int, C.c_int, _D, C.c_uint64,
+                                              C.c_int, _D, _D, _D, _D, P(C.c_int)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -5,10 +5,13 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 
 #include "gqmap_blockmatch.h"
+#include "gqmap_denoise.h"
 #include "gqmap_flowcheck.h"
 #include "gqmap_internal.h"
 #include "gqmap_rof.h"
@@ -778,6 +781,137 @@ gqmap_status gqmap_flow_fill_host(const double *flow, const unsigned char *mask,
     }
     std::memcpy(out, cur.data(), sizeof(double) * 2 * MN);
     if (filled) std::memcpy(filled, state.data(), MN);
+    return GQMAP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Weighted flow denoising, host model: the arithmetic of gqmap_denoise.h, the
+// two phases of an iteration (rules, then sum and step) each split over columns
+// among the threads.  A column's results depend on no other column of the same
+// phase and the maxima are taken on bit patterns, so the thread count shows in
+// no result.  Bit for bit what gqmap_flow_denoise computes.
+// ---------------------------------------------------------------------------
+namespace {
+
+int dn_threads()
+{
+    const char *e = std::getenv("GQMAP_HOST_THREADS");
+    int n = e ? std::atoi(e) : (int)std::min(16u, std::thread::hardware_concurrency());
+    return std::max(1, std::min(n, 256));
+}
+
+// fn(tid, n0, n1) over a static split of the columns [0, ncols) among nthreads
+template <class F>
+void dn_columns(int nthreads, int ncols, F fn)
+{
+    nthreads = std::max(1, std::min(nthreads, ncols));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nthreads; ++t)
+        pool.emplace_back(fn, t, (int)((int64_t)ncols * t / nthreads), (int)((int64_t)ncols * (t + 1) / nthreads));
+    fn(0, 0, (int)((int64_t)ncols / nthreads));
+    for (std::thread &th : pool) th.join();
+}
+
+template <int KT>
+int dn_host_run(const gqmap_cpu_options *o, const gq::DnRule &R, const double *flow, const double *var, int M, int N, bool adjoint, double *mu, double *sigma, double *rou, double *trace)
+{
+    const size_t MN = (size_t)M * N;
+    std::vector<double> dnode(4 * MN, 0.0), dedge(20 * MN, 0.0);
+    const int T = dn_threads();
+    std::vector<unsigned long long> mx(3 * (size_t)T);
+    int done = 0;
+    for (int it = 1;; ++it) {
+        dn_columns(T, N - 1, [&](int, int n0, int n1) {
+            for (int n = n0; n < n1; ++n)
+                for (int l = 0; l < 2; ++l)
+                    for (int m = 0; m < M - 1; ++m) {
+                        const size_t q = gq::dn_i3(M, N, m, n, l);
+                        const double o1 = sigma[q], u1 = mu[q], f = flow[q], v = var ? var[q] : o->var;
+                        double dn[2];
+                        gq::dn_node<KT, GQ_DN_VAR_FIELD>(R, std::sqrt(2.0) * o1, u1, f, v,
+                                                         gq::dn_observed(f, var != nullptr, v), dn);
+                        dnode[gq::dn_i4(M, N, m, n, 0, l)] = dn[0];
+                        dnode[gq::dn_i4(M, N, m, n, 1, l)] = dn[1];
+                        for (int j = 0; j < 2; ++j) {
+                            const size_t q2 = gq::dn_i3(M, N, m + (j == 0), n + (j == 1), l);
+                            double de[5];
+                            gq::dn_edge<KT, false, false>(R, rou[gq::dn_i4(M, N, m, n, j, l)], o1, u1, sigma[q2], mu[q2], de);
+                            for (int k = 0; k < 5; ++k) dedge[gq::dn_i5(M, N, m, n, j, k, l)] = de[k];
+                        }
+                    }
+        });
+        std::fill(mx.begin(), mx.end(), 0ull);
+        const double step = gq::dn_step(o->step0, it, o->step_decay);
+        dn_columns(T, N, [&](int tid, int n0, int n1) {
+            unsigned long long *r = &mx[3 * (size_t)tid];
+            for (int n = n0; n < n1; ++n)
+                for (int l = 0; l < 2; ++l)
+                    for (int m = 0; m < M; ++m) {
+                        double a, b;
+                        if (adjoint) gq::dn_gather<true>(dnode.data(), dedge.data(), M, N, m, n, l, a, b);
+                        else gq::dn_gather<false>(dnode.data(), dedge.data(), M, N, m, n, l, a, b);
+                        const double mp = gq::dn_apply(mu, sigma, rou, dedge.data(), M, N, m, n, l, a, b, step, o->corr_tor);
+                        r[0] = std::max(r[0], gq::dn_abits(a));
+                        r[1] = std::max(r[1], gq::dn_abits(b));
+                        r[2] = std::max(r[2], gq::dn_abits(mp));
+                    }
+        });
+        unsigned long long top[3] = {0, 0, 0};
+        for (int t = 0; t < T; ++t)
+            for (int k = 0; k < 3; ++k) top[k] = std::max(top[k], mx[3 * (size_t)t + k]);
+        if (trace)
+            for (int k = 0; k < 3; ++k) trace[3 * (size_t)(it - 1) + k] = gq::dn_from_bits(top[k]);
+        done = it;
+        if (gq::dn_stop(it, o->its, o->min_its, gq::dn_from_bits(top[0]), o->tor)) break;
+    }
+    return done;
+}
+
+}  // namespace
+
+extern "C" {
+
+gqmap_status gqmap_flow_denoise_host(const gqmap_cpu_options *o, const double *flow, const double *var,
+                                     const double *mu0, int M, int N, const double *sigma0, uint64_t seed,
+                                     int scatter, double *mu, double *sigma, double *rou, double *trace,
+                                     int *its_done)
+{
+    gq::clear_error();
+    const char *fn = "gqmap_flow_denoise_host";
+    GQ_CHECK(o && flow && mu && sigma && rou, GQMAP_ERR_INVALID_ARG, "%s: null argument", fn);
+    GQ_CHECK(M >= 2 && N >= 2, GQMAP_ERR_INVALID_ARG, "%s: flow %dx%d too small", fn, M, N);
+    GQ_CHECK(o->K >= 1 && o->K <= GQMAP_KMAX, GQMAP_ERR_INVALID_ARG, "K=%d outside [1,%d]", o->K, GQMAP_KMAX);
+    GQ_CHECK(o->its >= 1, GQMAP_ERR_INVALID_ARG, "its=%d", o->its);
+    GQ_CHECK(scatter == GQMAP_SCATTER_REFERENCE || scatter == GQMAP_SCATTER_ADJOINT, GQMAP_ERR_INVALID_ARG,
+             "%s: scatter=%d (0: reference, 1: adjoint)", fn, scatter);
+    const size_t MN = (size_t)M * N;
+    const double *start = mu0 ? mu0 : flow;
+    for (size_t i = 0; i < 2 * MN; ++i)
+        GQ_CHECK(gq::dn_finite(start[i]), GQMAP_ERR_INVALID_ARG, "%s: %s", fn,
+                 mu0 ? "mu0 must be finite everywhere" : "without mu0 the flow is the start and must be finite everywhere");
+    static_assert(GQMAP_KMAX == 16, "DnRule's arrays");
+    gq::DnRule R{};
+    R.K = o->K; R.gama = o->gama; R.dta = o->dta;
+    if (gq::gauss_hermite(o->K, R.X, R.W) != 0) {
+        gq::set_error("Gauss-Hermite did not converge for K=%d", o->K);
+        return GQMAP_ERR_INVALID_ARG;
+    }
+    for (int c = 0; c < o->K; ++c)
+        for (int r = 0; r < o->K; ++r) R.WW[r + o->K * c] = R.W[c] * R.W[r];  // WIWJ (:5-6)
+    std::memmove(mu, start, sizeof(double) * 2 * MN);
+    if (sigma0) {
+        std::memmove(sigma, sigma0, sizeof(double) * 2 * MN);
+    } else {
+        const uint64_t base = gq::stream_base(seed, 3);
+        for (size_t i = 0; i < 2 * MN; ++i) sigma[i] = gq::u01(base, (uint64_t)i) + 2;
+    }
+    std::fill(rou, rou + 4 * MN, 0.0);
+    const bool adjoint = scatter == GQMAP_SCATTER_ADJOINT;
+    const int done = o->K == 9 ? dn_host_run<9>(o, R, flow, var, M, N, adjoint, mu, sigma, rou, trace)
+                               : dn_host_run<0>(o, R, flow, var, M, N, adjoint, mu, sigma, rou, trace);
+    if (its_done) *its_done = done;
     return GQMAP_OK;
 }
 

@@ -14,12 +14,18 @@
 // No host round trip inside the loop.  Plain fp64 with contraction off in the
 // order of the MATLAB expressions, so the device matches the C restatement
 // (oracle/gqmap_legacy_oracle.c) bit for bit.
+//
+// gqmap_flow_denoise is the same loop with a variance field and an observation
+// select in the node rule, a start of its own and the adjoint scatter in the
+// sum (gqmap_denoise.h holds the rules of both): further instantiations of
+// k_legacy_grad / k_legacy_update, and k_legacy_finite once before the loop.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "gqmap_denoise.h"
 #include "gqmap_internal.h"
 
 #pragma clang fp contract(off)
@@ -31,6 +37,7 @@ constexpr int LG_KMAX = GQMAP_KMAX;
 
 struct LgParams {
     const double *flow;
+    const double *varf;           // the variance field (M x N x 2) or null: the scalar var
     double *mu, *sigma, *rou, *dnode, *dedge;
     unsigned long long *blkmax;   // [update workgroups][3]: |dmu|, |dsigma|, |drou| maxima as bits
     int *ctl;                     // it, stop, done
@@ -41,114 +48,47 @@ struct LgParams {
     double WW[LG_KMAX * LG_KMAX];  // W[c] * W[r] at r + K*c (WIWJ, :5-6), the host's product
 };
 
-__device__ __forceinline__ size_t i3(int M, int N, int m, int n, int l) { return m + (size_t)M * (n + (size_t)N * l); }
-__device__ __forceinline__ size_t i4(int M, int N, int m, int n, int a, int b)
-{
-    return m + (size_t)M * (n + (size_t)N * (a + 2 * (size_t)b));
-}
-__device__ __forceinline__ size_t i5(int M, int N, int m, int n, int j, int q, int l)
-{
-    return m + (size_t)M * (n + (size_t)N * (j + 2 * (q + 5 * (size_t)l)));
-}
-
 // One thread per node m < M-1, n < N-1, edge j and layer l ((j, l) slowest:
 // a wave stays on one edge of one layer): the edge rule (j, l) of the node,
 // and on the j = 0 threads the node rule of layer l too (9 of ~170 points).
-// Every expression keeps the reference's operand order; what is hoisted is a
-// whole subexpression of it, computed once with the same operands:
-//   s*XI, t*XI, ds*XI, dt*XI per column c and t*XJ, s*XJ, dt*XJ, ds*XJ per
-//   row r (when K is a template constant: held in registers), sq2*o1 and
-//   sq2*o2, WIWJ from the host table.
-// c2 (the sum of df2 = -df1) is 0 - c1 exactly: both start at +0, IEEE
-// addition is symmetric under negation, and an exact-zero sum is +0 in both
-// chains -- so column and total sums of df2 are not formed (s2 = 0 - s1).
-// KT: K as a template constant (0: P.K at run time); GAMA1 / VAR1: gama == 1
-// / var == 1, where x / 1 == x exactly; DTA_INF: dta == inf, where
-// fabs(diff) > dta is false for every diff (NaN included).
-template <int KT, bool GAMA1, bool VAR1, bool DTA_INF>
+// The rules are gqmap_denoise.h's, expanded here (see there why not called).
+// KT: K as a template constant (0: P.K at run time); GAMA1: gama == 1; VM: the
+// scalar var, var == 1, or the variance field P.varf with the observation
+// select (one more coalesced load on the node-rule threads; P.varf == NULL:
+// the scalar var, observed where the flow is finite); DTA_INF: dta == inf.
+template <int KT, bool GAMA1, int VM, bool DTA_INF>
 __global__ __launch_bounds__(256) void k_legacy_grad(LgParams P)
 {
     if (P.ctl[1]) return;
-    const int M = P.M, N = P.N, K = KT ? KT : P.K;
-    constexpr int UNR = KT ? KT : 1;  // full unroll for a constant K
+    const int M = P.M, N = P.N;
     const int64_t MN1 = (int64_t)(M - 1) * (N - 1);
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 4 * MN1) return;
     const int jl = (int)(t / MN1), j = jl & 1, l = jl >> 1;
     t -= jl * MN1;
     const int m = (int)(t % (M - 1)), n = (int)(t / (M - 1));
-    const double sq2 = sqrt(2.0), PI = 3.14159265358979323846;
-    const double o1 = P.sigma[i3(M, N, m, n, l)], u1 = P.mu[i3(M, N, m, n, l)];
-    const double so1 = sq2 * o1;
+    const double o1 = P.sigma[dn_i3(M, N, m, n, l)], u1 = P.mu[dn_i3(M, N, m, n, l)];
     if (j == 0) {  // (:20-26)
-        const double f = P.flow[i3(M, N, m, n, l)];
-        double du = 0, dsum = 0;
-#pragma unroll UNR
-        for (int k = 0; k < K; ++k) {
-            const double x = so1 * P.X[k] + u1;
-            const double dval = VAR1 ? P.W[k] * (f - x) : P.W[k] * (f - x) / P.var;
-            du += dval;
-            dsum += dval * P.X[k];
+        const double f = P.flow[dn_i3(M, N, m, n, l)];
+        double var = P.var;
+        bool obs = true;
+        if (VM == GQ_DN_VAR_FIELD) {
+            if (P.varf) var = P.varf[dn_i3(M, N, m, n, l)];
+            obs = dn_observed(f, P.varf != nullptr, var);
         }
-        P.dnode[i4(M, N, m, n, 0, l)] = du / sqrt(PI);
-        P.dnode[i4(M, N, m, n, 1, l)] = dsum * sqrt(2.0 / PI);
+        double dn[2];
+        GQ_DN_NODE_RULE(P, KT, VM, sqrt(2.0) * o1, u1, f, var, obs, dn);
+        P.dnode[dn_i4(M, N, m, n, 0, l)] = dn[0];
+        P.dnode[dn_i4(M, N, m, n, 1, l)] = dn[1];
     }
     {  // (:28-54)
         const int m2 = m + (j == 0), n2 = n + (j == 1);
-        const double p = P.rou[i4(M, N, m, n, j, l)];
-        const double o2 = P.sigma[i3(M, N, m2, n2, l)], u2 = P.mu[i3(M, N, m2, n2, l)];
-        const double so2 = sq2 * o2;
-        const double q = sqrt(1 + p), r = sqrt(1 - p);
-        const double s = (q + r) / 2, tt = (q - r) / 2;
-        const double ds = (1 / q - 1 / r) / 4, dt = (1 / q + 1 / r) / 4;
-        double txj[UNR], sxj[UNR], dtxj[UNR], dsxj[UNR];
-        if (KT) {
-#pragma unroll UNR
-            for (int rr = 0; rr < UNR; ++rr) {
-                txj[rr] = tt * P.X[rr];
-                sxj[rr] = s * P.X[rr];
-                dtxj[rr] = dt * P.X[rr];
-                dsxj[rr] = ds * P.X[rr];
-            }
-        }
-        double s1 = 0, so1s = 0, so2s = 0, sp = 0;
-#pragma unroll UNR
-        for (int c = 0; c < K; ++c) {  // sum(sum(A)): column sums first
-            const double xi = P.X[c];
-            const double sxi = s * xi, txi = tt * xi, dsxi = ds * xi, dtxi = dt * xi;
-            double c1 = 0, co1 = 0, co2 = 0, cp = 0;
-#pragma unroll UNR
-            for (int rr = 0; rr < K; ++rr) {
-                const double xj = P.X[rr];
-                const double tx = KT ? txj[rr] : tt * xj, sx = KT ? sxj[rr] : s * xj;
-                const double dtx = KT ? dtxj[rr] : dt * xj, dsx = KT ? dsxj[rr] : ds * xj;
-                const double ZI = sxi + tx, ZJ = txi + sx;
-                const double x1 = so1 * ZI + u1, x2 = so2 * ZJ + u2;
-                double diff = x2 - x1;
-                if (!DTA_INF && fabs(diff) > P.dta) diff = 0;  // (:44)
-                const double ww = P.WW[rr + K * c];
-                const double df1 = GAMA1 ? ww * diff : ww * diff / P.gama, df2 = -df1;
-                c1 += df1;
-                co1 += df1 * ZI;
-                co2 += df2 * ZJ;
-                cp += o1 * df1 * (dsxi + dtx) + o2 * df2 * (dtxi + dsx);
-            }
-            s1 += c1; so1s += co1; so2s += co2; sp += cp;
-        }
-        const double s2 = 0.0 - s1;
-        P.dedge[i5(M, N, m, n, j, 0, l)] = 1 / PI * s1;
-        P.dedge[i5(M, N, m, n, j, 1, l)] = 1 / PI * s2;
-        P.dedge[i5(M, N, m, n, j, 2, l)] = 1 / PI * sq2 * so1s;
-        P.dedge[i5(M, N, m, n, j, 3, l)] = 1 / PI * sq2 * so2s;
-        P.dedge[i5(M, N, m, n, j, 4, l)] = 1 / PI * sq2 * sp;
+        const double p = P.rou[dn_i4(M, N, m, n, j, l)];
+        const double o2 = P.sigma[dn_i3(M, N, m2, n2, l)], u2 = P.mu[dn_i3(M, N, m2, n2, l)];
+        double de[5];
+        GQ_DN_EDGE_RULE(P, KT, GAMA1, DTA_INF, p, o1, u1, o2, u2, de);
+        for (int q = 0; q < 5; ++q) P.dedge[dn_i5(M, N, m, n, j, q, l)] = de[q];
     }
-}
-
-// |v| as its bit pattern: for |v| >= 0 (and NaN above +inf) the unsigned
-// order of the bits is the order of the values, so max is exact in any order
-__device__ __forceinline__ unsigned long long abits(double v)
-{
-    return (unsigned long long)__double_as_longlong(fabs(v));
 }
 
 // Maximum over the block of three bit patterns (thread 0 holds the result).
@@ -176,6 +116,9 @@ __device__ void block_max3(unsigned long long &a, unsigned long long &b, unsigne
 // atomicMax per workgroup on three shared addresses serialises in L2, and a
 // last-workgroup reduction needs a device-scope release per workgroup, an L2
 // writeback each -- 70 us per launch) and k_legacy_ctl reduces the rows.
+// ADJ: the adjoint scatter of gqmap_denoise.h (dn_gather), otherwise the
+// reference's own shift.
+template <bool ADJ>
 __global__ __launch_bounds__(256) void k_legacy_update(LgParams P)
 {
     if (P.ctl[1]) return;
@@ -187,28 +130,10 @@ __global__ __launch_bounds__(256) void k_legacy_update(LgParams P)
     double a = 0, b = 0, mp = 0;
     if (t < (int64_t)M * N * 2) {
         const int m = (int)(t % M), n = (int)((t / M) % N), l = (int)(t / ((int64_t)M * N));
-        const double *de = P.dedge;
-        // (:58-59) dmu = dnode + sum_j dedge(:,:,j,1) + (dedge(m+1,n,1,2) + dedge(m,n+1,2,2))
-        a = P.dnode[i4(M, N, m, n, 0, l)] + (de[i5(M, N, m, n, 0, 0, l)] + de[i5(M, N, m, n, 1, 0, l)]);
-        b = P.dnode[i4(M, N, m, n, 1, l)] + (de[i5(M, N, m, n, 0, 2, l)] + de[i5(M, N, m, n, 1, 2, l)]);
-        const double nu = m + 1 < M ? de[i5(M, N, m + 1, n, 0, 1, l)] : 0.0;
-        const double nl = n + 1 < N ? de[i5(M, N, m, n + 1, 1, 1, l)] : 0.0;
-        const double su = m + 1 < M ? de[i5(M, N, m + 1, n, 0, 3, l)] : 0.0;
-        const double sl = n + 1 < N ? de[i5(M, N, m, n + 1, 1, 3, l)] : 0.0;
-        a = a + (nu + nl);
-        b = b + (su + sl);
-        const double step = P.step0 / (1 + it / P.step_decay);  // (:62)
-        const size_t q = i3(M, N, m, n, l);
-        P.mu[q] = P.mu[q] + a * step;               // (:63)
-        P.sigma[q] = fabs(P.sigma[q] + b * step);   // (:64)
-        for (int j = 0; j < 2; ++j) {               // (:65)
-            const double d = de[i5(M, N, m, n, j, 4, l)];
-            mp = fmax(mp, fabs(d));
-            const size_t r = i4(M, N, m, n, j, l);
-            P.rou[r] = fmax(fmin(P.rou[r] + d * step, P.corr), -P.corr);
-        }
+        dn_gather<ADJ>(P.dnode, P.dedge, M, N, m, n, l, a, b);
+        mp = dn_apply(P.mu, P.sigma, P.rou, P.dedge, M, N, m, n, l, a, b, dn_step(P.step0, it, P.step_decay), P.corr);
     }
-    unsigned long long ba = abits(a), bb = abits(b), bm = abits(mp);
+    unsigned long long ba = dn_abits(a), bb = dn_abits(b), bm = dn_abits(mp);
     block_max3(ba, bb, bm);
     if (threadIdx.x == 0) {
         unsigned long long *row = P.blkmax + 3 * (size_t)blockIdx.x;
@@ -216,6 +141,16 @@ __global__ __launch_bounds__(256) void k_legacy_update(LgParams P)
         row[1] = bb;
         row[2] = bm;
     }
+}
+
+// Is any entry of a (or of b, which may be null) NaN or +-Inf?  flags[0] / flags[1]
+// are zero on entry; every thread that finds one stores the same 1.
+__global__ __launch_bounds__(256) void k_legacy_finite(const double *a, const double *b, int64_t n, int *flags)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!dn_finite(a[i])) flags[0] = 1;
+    if (b && !dn_finite(b[i])) flags[1] = 1;
 }
 
 // sigma = rand(M,N,2) + 2 (:10) from the library RNG stream 3: the host
@@ -244,12 +179,12 @@ __global__ __launch_bounds__(1024) void k_legacy_ctl(LgParams P)
     const unsigned long long bits[3] = {a, b, c};
     double mx[3];
     for (int q = 0; q < 3; ++q) {
-        mx[q] = __longlong_as_double((long long)bits[q]);
+        mx[q] = dn_from_bits(bits[q]);
         P.trace[3 * (it - 1) + q] = mx[q];
     }
     P.ctl[0] = it + 1;
     P.ctl[2] = it;
-    if (it + 1 > P.its || (it + 1 > P.min_its && mx[0] < P.tor)) P.ctl[1] = 1;  // (:70)
+    if (dn_stop(it, P.its, P.min_its, mx[0], P.tor)) P.ctl[1] = 1;  // (:70)
 }
 
 // One device arena per host thread and device, kept across calls: the nine
@@ -337,14 +272,22 @@ bool overlap(const void *a, size_t na, const void *b, size_t nb)
 // gqmap_cpu_run (DEV = false: host arrays, copied in and out) and
 // gqmap_cpu_run_device (DEV = true: flow / sigma0 / mu / sigma / rou / trace
 // are device arrays; the iteration runs on mu / sigma / rou in place).
-gqmap_status cpu_run(const gqmap_cpu_options *o, const double *flow, int M, int N, const double *sigma0, uint64_t seed,
-                     double *mu, double *sigma, double *rou, double *trace, int *its_done, int device, bool DEV)
+// DENOISE: gqmap_flow_denoise / gqmap_flow_denoise_device -- var and mu0 (each
+// may be null) join the inputs, the start is checked by k_legacy_finite before
+// the loop, scatter chooses the sum.  Without DENOISE var and mu0 are null,
+// scatter is the reference's and nothing is checked: gqmap_cpu_run as it was.
+gqmap_status cpu_run(const gqmap_cpu_options *o, const double *flow, const double *var, const double *mu0, int M, int N,
+                     const double *sigma0, uint64_t seed, int scatter, double *mu, double *sigma, double *rou,
+                     double *trace, int *its_done, int device, bool DEV, bool DENOISE)
 {
-    const char *fn = DEV ? "gqmap_cpu_run_device" : "gqmap_cpu_run";
+    const char *fn = DENOISE ? (DEV ? "gqmap_flow_denoise_device" : "gqmap_flow_denoise")
+                             : (DEV ? "gqmap_cpu_run_device" : "gqmap_cpu_run");
     GQ_CHECK(o && flow && mu && sigma && rou, GQMAP_ERR_INVALID_ARG, "%s: null argument", fn);
     GQ_CHECK(M >= 2 && N >= 2, GQMAP_ERR_INVALID_ARG, "%s: flow %dx%d too small", fn, M, N);
     GQ_CHECK(o->K >= 1 && o->K <= GQMAP_KMAX, GQMAP_ERR_INVALID_ARG, "K=%d outside [1,%d]", o->K, GQMAP_KMAX);
     GQ_CHECK(o->its >= 1, GQMAP_ERR_INVALID_ARG, "its=%d", o->its);
+    GQ_CHECK(scatter == GQMAP_SCATTER_REFERENCE || scatter == GQMAP_SCATTER_ADJOINT, GQMAP_ERR_INVALID_ARG,
+             "%s: scatter=%d (0: reference, 1: adjoint)", fn, scatter);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         set_error("no HIP device available");
@@ -357,21 +300,23 @@ gqmap_status cpu_run(const gqmap_cpu_options *o, const double *flow, int M, int 
     if (DEV) {
         GQ_CHECK(on_device(flow, device) && on_device(mu, device) && on_device(sigma, device) &&
                      on_device(rou, device) && (!sigma0 || on_device(sigma0, device)) &&
-                     (!trace || on_device(trace, device)),
+                     (!trace || on_device(trace, device)) && (!var || on_device(var, device)) &&
+                     (!mu0 || on_device(mu0, device)),
                  GQMAP_ERR_INVALID_ARG, "%s: every array must be device memory of device %d", fn, device);
         // the outputs (written in place during the run) must not overlap each
         // other or an input
         const size_t b2 = sizeof(double) * 2 * MN;
         const struct { const void *p; size_t n; } out[4] = {
             {mu, b2}, {sigma, b2}, {rou, 2 * b2}, {trace, trace ? sizeof(double) * 3 * (size_t)o->its : 0}};
-        const struct { const void *p; size_t n; } in[2] = {{flow, b2}, {sigma0, sigma0 ? b2 : 0}};
+        const struct { const void *p; size_t n; const char *name; } in[4] = {
+            {flow, b2, "flow"}, {sigma0, sigma0 ? b2 : 0, "sigma0"}, {var, var ? b2 : 0, "var"}, {mu0, mu0 ? b2 : 0, "mu0"}};
         for (int i = 0; i < 4; ++i) {
             for (int j = i + 1; j < 4; ++j)
                 GQ_CHECK(!overlap(out[i].p, out[i].n, out[j].p, out[j].n), GQMAP_ERR_INVALID_ARG,
                          "%s: output arrays %d and %d overlap (mu, sigma, rou, trace)", fn, i, j);
-            for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 4; ++j)
                 GQ_CHECK(!overlap(out[i].p, out[i].n, in[j].p, in[j].n), GQMAP_ERR_INVALID_ARG,
-                         "%s: output array %d (mu, sigma, rou, trace) overlaps %s", fn, i, j ? "sigma0" : "flow");
+                         "%s: output array %d (mu, sigma, rou, trace) overlaps %s", fn, i, in[j].name);
         }
     }
     LgParams P{};
@@ -391,13 +336,14 @@ gqmap_status cpu_run(const gqmap_cpu_options *o, const double *flow, int M, int 
     // are carved from it, so a repeated call pays no hipMalloc/hipFree (they
     // dominated a 50-iteration call's wall clock).
     struct Buf { void *p = nullptr; };
-    Buf bflow, bmu, bsg, brou, bdn, bde, bmax, bctl, btr;
-    const size_t io = DEV ? 0 : 1, tr = DEV && trace ? 0 : 1;
-    const size_t sizes[9] = {io * sizeof(double) * 2 * MN, io * sizeof(double) * 2 * MN, io * sizeof(double) * 2 * MN,
-                             io * sizeof(double) * 4 * MN, sizeof(double) * 4 * MN, sizeof(double) * 20 * MN,
-                             sizeof(unsigned long long) * 3 * (size_t)nblk, sizeof(int) * 4,
-                             tr * sizeof(double) * 3 * (size_t)o->its};
-    Buf *bufs[9] = {&bflow, &bmu, &bsg, &brou, &bdn, &bde, &bmax, &bctl, &btr};
+    Buf bflow, bmu, bsg, brou, bdn, bde, bmax, bctl, btr, bvar;
+    const size_t io = DEV ? 0 : 1, tr = DEV && trace ? 0 : 1, vf = !DEV && var ? 1 : 0;
+    constexpr int NBUF = 10;
+    const size_t sizes[NBUF] = {io * sizeof(double) * 2 * MN, io * sizeof(double) * 2 * MN, io * sizeof(double) * 2 * MN,
+                                io * sizeof(double) * 4 * MN, sizeof(double) * 4 * MN, sizeof(double) * 20 * MN,
+                                sizeof(unsigned long long) * 3 * (size_t)nblk, sizeof(int) * 8,
+                                tr * sizeof(double) * 3 * (size_t)o->its, vf * sizeof(double) * 2 * MN};
+    Buf *bufs[NBUF] = {&bflow, &bmu, &bsg, &brou, &bdn, &bde, &bmax, &bctl, &btr, &bvar};
     size_t need = 0;
     for (size_t sz : sizes) need += (sz + 255) & ~(size_t)255;
     Arena &A = g_arenas[device];
@@ -410,7 +356,7 @@ gqmap_status cpu_run(const gqmap_cpu_options *o, const double *flow, int M, int 
         A.cap = cap;
     }
     size_t off = 0;
-    for (int i = 0; i < 9; ++i) {
+    for (int i = 0; i < NBUF; ++i) {
         bufs[i]->p = (char *)A.p + off;
         off += (sizes[i] + 255) & ~(size_t)255;
     }
@@ -422,10 +368,28 @@ gqmap_status cpu_run(const gqmap_cpu_options *o, const double *flow, int M, int 
         if (trace) btr.p = trace;
     } else {
         GQ_HIP(hipMemcpy(bflow.p, flow, sizeof(double) * 2 * MN, hipMemcpyHostToDevice));
+        if (var) GQ_HIP(hipMemcpy(bvar.p, var, sizeof(double) * 2 * MN, hipMemcpyHostToDevice));
     }
-    // mu = flow (:9); sigma = rand(M,N,2) + 2 (:10, library RNG stream 3,
-    // drawn on the device) unless given; rou = 0 (:11)
-    GQ_HIP(hipMemcpy(bmu.p, bflow.p, sizeof(double) * 2 * MN, hipMemcpyDeviceToDevice));
+    const int ctl0[8] = {1, 0, 0, 0, 0, 0, 0, 0};  // it, stop, done, -, start not finite, flow not finite
+    GQ_HIP(hipMemcpy(bctl.p, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+    // the start: mu0 (host arrays: uploaded straight into the arena's mu) or the flow
+    const bool up = !DEV && mu0;
+    if (up) GQ_HIP(hipMemcpy(bmu.p, mu0, sizeof(double) * 2 * MN, hipMemcpyHostToDevice));
+    const double *start = mu0 ? (DEV ? mu0 : (const double *)bmu.p) : (const double *)bflow.p;
+    bool flow_finite = true;
+    if (DENOISE) {  // before anything is written to an output
+        k_legacy_finite<<<(int)((2 * MN + 255) / 256), 256>>>(start, mu0 ? (const double *)bflow.p : nullptr,
+                                                             (int64_t)(2 * MN), (int *)bctl.p + 4);
+        GQ_HIP(hipGetLastError());
+        int flags[2];
+        GQ_HIP(hipMemcpy(flags, (int *)bctl.p + 4, sizeof(flags), hipMemcpyDeviceToHost));
+        GQ_CHECK(!flags[0], GQMAP_ERR_INVALID_ARG, "%s: %s", fn,
+                 mu0 ? "mu0 must be finite everywhere" : "without mu0 the flow is the start and must be finite everywhere");
+        flow_finite = !flags[1];
+    }
+    // mu = flow (:9) or mu0; sigma = rand(M,N,2) + 2 (:10, library RNG stream
+    // 3, drawn on the device) unless given; rou = 0 (:11)
+    if (!up) GQ_HIP(hipMemcpy(bmu.p, start, sizeof(double) * 2 * MN, hipMemcpyDeviceToDevice));
     if (sigma0)
         GQ_HIP(hipMemcpy(bsg.p, sigma0, sizeof(double) * 2 * MN, DEV ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     else
@@ -433,27 +397,30 @@ gqmap_status cpu_run(const gqmap_cpu_options *o, const double *flow, int M, int 
     GQ_HIP(hipMemset(brou.p, 0, sizeof(double) * 4 * MN));
     GQ_HIP(hipMemset(bdn.p, 0, sizeof(double) * 4 * MN));   // dnode = zeros (:14): last row/col stay 0
     GQ_HIP(hipMemset(bde.p, 0, sizeof(double) * 20 * MN));  // dedge = zeros (:15)
-    const int ctl0[4] = {1, 0, 0, 0};
-    GQ_HIP(hipMemcpy(bctl.p, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+    P.varf = var ? (DEV ? var : (const double *)bvar.p) : nullptr;
     P.flow = (const double *)bflow.p; P.mu = (double *)bmu.p; P.sigma = (double *)bsg.p; P.rou = (double *)brou.p;
     P.dnode = (double *)bdn.p; P.dedge = (double *)bde.p; P.blkmax = (unsigned long long *)bmax.p;
     P.ctl = (int *)bctl.p; P.trace = (double *)btr.p;
     // the grad kernel's compile-time variants: K = 9 (the reference's) or any
-    // K; gama / var == 1; dta == inf (the defaults)
-    using Grad = void (*)(LgParams);
-    static constexpr Grad kGrad[2][2][2][2] = {
-        {{{k_legacy_grad<0, false, false, false>, k_legacy_grad<0, false, false, true>},
-          {k_legacy_grad<0, false, true, false>, k_legacy_grad<0, false, true, true>}},
-         {{k_legacy_grad<0, true, false, false>, k_legacy_grad<0, true, false, true>},
-          {k_legacy_grad<0, true, true, false>, k_legacy_grad<0, true, true, true>}}},
-        {{{k_legacy_grad<9, false, false, false>, k_legacy_grad<9, false, false, true>},
-          {k_legacy_grad<9, false, true, false>, k_legacy_grad<9, false, true, true>}},
-         {{k_legacy_grad<9, true, false, false>, k_legacy_grad<9, true, false, true>},
-          {k_legacy_grad<9, true, true, false>, k_legacy_grad<9, true, true, true>}}}};
-    const Grad grad = kGrad[P.K == 9][P.gama == 1.0][P.var == 1.0][P.dta == INFINITY];
+    // K; gama / var == 1; dta == inf (the defaults).  The variance-field
+    // variant (with its observation select) runs only where it is needed: a
+    // field is given, or the flow holds an entry that is not finite.  Every
+    // other call -- gqmap_cpu_run always -- takes the scalar variants.
+    using Kern = void (*)(LgParams);
+#define GQ_LG_ROW(KT, G) \
+    {{k_legacy_grad<KT, G, 0, false>, k_legacy_grad<KT, G, 0, true>}, \
+     {k_legacy_grad<KT, G, 1, false>, k_legacy_grad<KT, G, 1, true>}, \
+     {k_legacy_grad<KT, G, 2, false>, k_legacy_grad<KT, G, 2, true>}}
+    static constexpr Kern kGrad[2][2][3][2] = {{GQ_LG_ROW(0, false), GQ_LG_ROW(0, true)},
+                                               {GQ_LG_ROW(9, false), GQ_LG_ROW(9, true)}};
+#undef GQ_LG_ROW
+    static_assert(GQ_DN_VAR_SCALAR == 0 && GQ_DN_VAR_ONE == 1 && GQ_DN_VAR_FIELD == 2, "kGrad's third index");
+    const int vm = P.varf || !flow_finite ? GQ_DN_VAR_FIELD : P.var == 1.0 ? GQ_DN_VAR_ONE : GQ_DN_VAR_SCALAR;
+    const Kern grad = kGrad[P.K == 9][P.gama == 1.0][vm][P.dta == INFINITY];
+    const Kern update = scatter == GQMAP_SCATTER_ADJOINT ? k_legacy_update<true> : k_legacy_update<false>;
     for (int it = 0; it < o->its; ++it) {
         grad<<<g1, 256>>>(P);
-        k_legacy_update<<<nblk, 256>>>(P);
+        update<<<nblk, 256>>>(P);
         k_legacy_ctl<<<1, 1024>>>(P);
     }
     GQ_HIP(hipGetLastError());
@@ -480,7 +447,8 @@ gqmap_status gqmap_cpu_run(const gqmap_cpu_options *o, const double *flow, int M
                            int device)
 {
     clear_error();
-    return cpu_run(o, flow, M, N, sigma0, seed, mu, sigma, rou, trace, its_done, device, false);
+    return cpu_run(o, flow, nullptr, nullptr, M, N, sigma0, seed, GQMAP_SCATTER_REFERENCE, mu, sigma, rou, trace,
+                   its_done, device, false, false);
 }
 
 gqmap_status gqmap_cpu_run_device(const gqmap_cpu_options *o, const double *flow, int M, int N,
@@ -488,7 +456,25 @@ gqmap_status gqmap_cpu_run_device(const gqmap_cpu_options *o, const double *flow
                                   double *trace, int *its_done, int device)
 {
     clear_error();
-    return cpu_run(o, flow, M, N, sigma0, seed, mu, sigma, rou, trace, its_done, device, true);
+    return cpu_run(o, flow, nullptr, nullptr, M, N, sigma0, seed, GQMAP_SCATTER_REFERENCE, mu, sigma, rou, trace,
+                   its_done, device, true, false);
+}
+
+gqmap_status gqmap_flow_denoise(const gqmap_cpu_options *o, const double *flow, const double *var, const double *mu0,
+                                int M, int N, const double *sigma0, uint64_t seed, int scatter, double *mu,
+                                double *sigma, double *rou, double *trace, int *its_done, int device)
+{
+    clear_error();
+    return cpu_run(o, flow, var, mu0, M, N, sigma0, seed, scatter, mu, sigma, rou, trace, its_done, device, false, true);
+}
+
+gqmap_status gqmap_flow_denoise_device(const gqmap_cpu_options *o, const double *flow, const double *var,
+                                       const double *mu0, int M, int N, const double *sigma0, uint64_t seed,
+                                       int scatter, double *mu, double *sigma, double *rou, double *trace,
+                                       int *its_done, int device)
+{
+    clear_error();
+    return cpu_run(o, flow, var, mu0, M, N, sigma0, seed, scatter, mu, sigma, rou, trace, its_done, device, true, true);
 }
 
 }  // extern "C"

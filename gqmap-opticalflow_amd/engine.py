@@ -611,6 +611,43 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     return (flow, ranges, np.asfortranarray(sig)) + tail
 
 
+def block_match_flow(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, levels: int = 1, pyr_r: int = 1,
+                     pyr_k: int = 1, var_scale: float = 1.0, var_default: float = 1.0, weighted: bool = True,
+                     denoise: dict | None = None, device: int = 0, host: bool = False):
+    """A flow from two frames alone: the block-matching start, checked both
+    ways and refilled, then denoised.  block_match_init(subpixel=True,
+    sigma_from_cost=True, consistency=True, fill=True) with U, V, ft, sigma,
+    levels, pyr_r and pyr_k passed through, then ops.flow_denoise on
+      observation  the refilled rank-0 flow; weighted=True: NaN (unobserved)
+                   where the pixel is inconsistent, so a refilled pixel is moved
+                   by its neighbours alone;
+      variance     var_scale * sigma^2 where the cost-derived sigma is finite,
+                   var_default elsewhere; weighted=False: var_default everywhere;
+      start        the refilled flow, 0.0 where it is still NaN.
+    denoise: the options of flow_denoise (default its=40; the other knobs of
+    gqmap_cpu), and optionally its keywords scatter, seed, sigma0 and
+    check_step.  var_scale is a knob nobody has tuned: the cost-derived widths
+    are Laplace estimates under the engine's data term, not calibrated errors.
+    Returns (flow, sigma, consistent): the denoised mean and its width
+    (M x N x 2) and the forward-backward verdict (M x N bool).  host=True runs
+    every stage on the library's host models (no device; bit-identical)."""
+    from .ops import flow_denoise
+    start, _, sig, cons = block_match_init(I1, I2, U, V, ft, sigma, device=device, host=host, subpixel=True,
+                                           sigma_from_cost=True, consistency=True, fill=True, levels=levels,
+                                           pyr_r=pyr_r, pyr_k=pyr_k)
+    kw = dict(denoise or {})
+    call = {k: kw.pop(k) for k in ("scatter", "seed", "sigma0", "check_step") if k in kw}
+    kw.setdefault("its", 40)
+    obs = np.where(cons[:, :, None], start, np.nan) if weighted else start
+    with np.errstate(invalid="ignore"):
+        var = np.where(np.isfinite(sig), float(var_scale) * sig * sig, float(var_default))
+    if not weighted:
+        var = np.full(start.shape, float(var_default))
+    mu0 = np.where(np.isnan(start), 0.0, start)
+    mu, sg, _ = flow_denoise(obs, var, mu0, options=kw, device=device, host=host, **call)
+    return mu, sg, cons
+
+
 def _mean_of_known(x, axis):
     """Mean over the entries that are not NaN; NaN where there are none."""
     known = ~np.isnan(x)

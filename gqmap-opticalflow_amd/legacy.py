@@ -107,3 +107,48 @@ def gqmap_cpu_device(options: dict, flow, *, sigma0=None, seed: int = 0, return_
 def release() -> None:
     """Free the calling thread's device arenas of gqmap_cpu (gqmap_cpu_release)."""
     check(_lib.load().gqmap_cpu_release(), "gqmap_cpu_release")
+
+
+def flow_denoise_device(flow, var=None, mu0=None, sigma0=None, options=None, scatter: str = "adjoint", seed: int = 0,
+                        return_trace: bool = False, check_step: bool = True):
+    """ops.flow_denoise on device arrays (gqmap_flow_denoise_device): flow, var,
+    mu0 and sigma0 (each of the last three may be None) are M x N x 2 float64
+    tensors on one HIP device, column-major as gqmap_cpu_device's.  Returns mu,
+    sigma, rou as device tensors in the same layout (and the its_done x 3
+    trace) -- no host copies, the same bits as flow_denoise.  The inputs are
+    left as they were; the start is checked on the device before anything is
+    written."""
+    import torch
+
+    from .ops import _scatter_code, denoise_step_bound
+    M, N = int(flow.shape[0]), int(flow.shape[1])
+    _check_dev("flow", flow, (M, N, 2))
+    for name, t in (("var", var), ("mu0", mu0), ("sigma0", sigma0)):
+        if t is not None:
+            _check_dev(name, t, (M, N, 2))
+            if t.device != flow.device:
+                raise ValueError(f"{name} is on {t.device}, flow on {flow.device}: one device")
+    o = cpu_options(options)
+    code = _scatter_code(scatter)
+    dev = flow.device
+    if check_step:
+        seen = torch.isfinite(flow)
+        if var is not None:
+            seen &= torch.isfinite(var) & (var > 0)
+        vmin = None if not bool(seen.any()) else float(var[seen].min()) if var is not None else o.var
+        bound = denoise_step_bound(o, vmin)
+        if not bound < 2:
+            raise ValueError(f"flow_denoise_device: step0 (1 / min observed var + 8 / gama) = {bound:g} >= 2: the ascent "
+                             "is linearly unstable (see flow_denoise); pass check_step=False to run it anyway")
+    mu, sigma, rou = _fortran_dev((M, N, 2), dev), _fortran_dev((M, N, 2), dev), _fortran_dev((M, N, 2, 2), dev)
+    trace = torch.empty((max(o.its, 1), 3), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)  # as gqmap_cpu_device: the library runs on its own queue
+    done = C.c_int(0)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    check(_lib.load().gqmap_flow_denoise_device(C.byref(o), flow.data_ptr(), ptr(var), ptr(mu0), M, N, ptr(sigma0),
+                                                C.c_uint64(seed), code, mu.data_ptr(), sigma.data_ptr(), rou.data_ptr(),
+                                                trace.data_ptr(), C.byref(done), dev.index if dev.index is not None else 0),
+          "gqmap_flow_denoise_device")
+    if return_trace:
+        return mu, sigma, rou, trace[:done.value]
+    return mu, sigma, rou

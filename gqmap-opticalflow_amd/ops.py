@@ -12,6 +12,7 @@ block_match_pyramid  coarse-to-fine block matching on block_match_window
 structure_texture  ROF structure-texture frames (optical_flowSuper.m:7-14, preprocessed=true)
 flow_consistency   forward-backward check of two flows (csrc/gqmap_flowcheck.h)
 flow_fill          rejected pixels refilled from the valid ones around them
+flow_denoise       weighted flow denoising: per-pixel variance, missing data, adjoint scatter (csrc/gqmap_denoise.h)
 """
 from __future__ import annotations
 
@@ -347,3 +348,90 @@ def preprocess_pair(I1, I2, **kw):
         raise ValueError("preprocess_pair returns the two texture frames only")
     tex = structure_texture(np.stack([I1, I2], axis=2), **kw)
     return np.asfortranarray(tex[:, :, 0]), np.asfortranarray(tex[:, :, 1])
+
+
+def _scatter_code(scatter) -> int:
+    codes = {"reference": _lib.SCATTER_REFERENCE, "adjoint": _lib.SCATTER_ADJOINT}
+    if scatter not in codes:
+        raise ValueError(f"flow_denoise: scatter must be 'reference' or 'adjoint', got {scatter!r}")
+    return codes[scatter]
+
+
+def denoise_step_bound(o, min_var) -> float:
+    """step0 (1 / min observed var + 8 / gama): the ascent of flow_denoise is
+    linearly stable while this stays below 2.  min_var None: nothing is observed."""
+    return o.step0 * ((0.0 if min_var is None else 1.0 / min_var) + 8.0 / o.gama)
+
+
+def flow_denoise(flow, var=None, mu0=None, sigma0=None, options=None, scatter: str = "adjoint", seed: int = 0,
+                 device: int = 0, host: bool = False, return_trace: bool = False, check_step: bool = True):
+    """Weighted flow denoising (gqmap_flow_denoise; csrc/gqmap_denoise.h holds
+    the specification): the engine of gqmap_cpu -- a Gaussian observation of a
+    flow under truncated-quadratic pairwise terms -- with a variance per pixel
+    and axis, missing observations, a start of its own and a choice of scatter.
+    Returns (mu, sigma, rou), shaped as gqmap_cpu's; return_trace=True appends
+    the its_done x 3 trace of max|dmu|, max|dsigma|, max|drou|.
+
+    flow, var, mu0, sigma0: M x N x 2, plane 0 horizontal.  An entry is observed
+    iff flow is finite, var is finite and var > 0 (var=None: iff flow is finite,
+    at options["var"]).  An unobserved entry is moved by its edges alone
+    (inpainting); what flow and var hold there reaches nothing.  mu0 is the
+    start and must be finite; mu0=None starts from flow, which must then be
+    finite.  sigma0=None draws U(0,1) + 2 from the library RNG (seed).
+    options: the knobs of gqmap_cpu (its, K, var, gama, dta, step0, step_decay,
+    corr_tor, tor, min_its).
+
+    scatter="reference" is legacy/gqmap_cpu.m:58-59 as written, which hands an
+    edge's second-endpoint gradient to the node two places before that
+    endpoint: a shifted second difference that amplifies low frequencies
+    ("Weighted flow denoising"); with var=None and mu0=None it is
+    gqmap_cpu bit for bit.  scatter="adjoint" hands it to the endpoint.  The
+    last row and column own no node term and no edge (the reference's loop
+    bounds): under "adjoint" they hang on one edge each.
+
+    Step bound.  To first order the ascent is mu <- mu + step (D + L) mu with
+    D = -1/var on the observed entries and L the 4-connected graph Laplacian
+    over gama, whose eigenvalues reach -8/gama.  The explicit step is stable
+    only while step0 (1 / min observed var + 8 / gama) < 2; at or above it the
+    highest frequency grows at every iteration, whatever the data.  The call
+    raises ValueError there; check_step=False skips the test.
+
+    host=True runs the library's host model (no device; bit-identical),
+    threaded over columns (GQMAP_HOST_THREADS; the result does not depend on
+    it)."""
+    from .legacy import cpu_options
+    flow = f64(flow)
+    if flow.ndim != 3 or flow.shape[2] != 2:
+        raise ValueError("flow must be M x N x 2")
+    M, N, _ = flow.shape
+    o = cpu_options(options)
+    code = _scatter_code(scatter)
+    opt = {}
+    for name, a in (("var", var), ("mu0", mu0), ("sigma0", sigma0)):
+        opt[name] = None if a is None else f64(a)
+        if opt[name] is not None and opt[name].shape != (M, N, 2):
+            raise ValueError(f"{name} must be {M} x {N} x 2 like flow, got {opt[name].shape}")
+    if check_step:
+        with np.errstate(invalid="ignore"):
+            seen = np.isfinite(flow)
+            if opt["var"] is not None:
+                seen &= np.isfinite(opt["var"]) & (opt["var"] > 0)
+        vmin = None if not seen.any() else float(opt["var"][seen].min()) if opt["var"] is not None else o.var
+        bound = denoise_step_bound(o, vmin)
+        if not bound < 2:
+            raise ValueError(f"flow_denoise: step0 (1 / min observed var + 8 / gama) = {bound:g} >= 2 (step0 = {o.step0:g}, "
+                             f"min observed var = {vmin}, gama = {o.gama:g}): the ascent is linearly unstable; lower "
+                             "step0, raise gama or the variances, or pass check_step=False")
+    mu = np.zeros((M, N, 2), order="F")
+    sigma = np.zeros((M, N, 2), order="F")
+    rou = np.zeros((M, N, 2, 2), order="F")
+    trace = np.zeros((max(o.its, 1), 3))
+    done = C.c_int(0)
+    ptr = lambda a: dptr(a) if a is not None else None
+    name = "gqmap_flow_denoise" + ("_host" if host else "")
+    check(getattr(_lib.load(), name)(C.byref(o), dptr(flow), ptr(opt["var"]), ptr(opt["mu0"]), M, N, ptr(opt["sigma0"]),
+                                     C.c_uint64(seed), code, dptr(mu), dptr(sigma), dptr(rou), dptr(trace),
+                                     C.byref(done), *(() if host else (device,))), name)
+    if return_trace:
+        return mu, sigma, rou, trace[:done.value]
+    return mu, sigma, rou

@@ -567,6 +567,49 @@ gqmap_status gqmap_cpu_run_device(const gqmap_cpu_options *o, const double *flow
  * MATLAB runtime owns its gpuArray pool). */
 gqmap_status gqmap_cpu_release(void);
 
+/* ---- weighted flow denoising (csrc/gqmap_denoise.h holds the specification) ----
+ * The engine above with a variance per pixel and axis, missing observations, a
+ * start of its own and a choice of how an edge's second-endpoint gradient is
+ * handed out.  flow (the observation), var (or NULL), mu0 (or NULL) and sigma0
+ * (or NULL) are M x N x 2, column-major, plane 0 horizontal.
+ *   observation  entry (m, n, l) is observed iff flow is finite, var is finite
+ *                and var > 0 (var == NULL: iff flow is finite, at o->var).  An
+ *                unobserved entry has a node gradient of exactly +0 and is moved
+ *                by its edges alone; what flow and var store there reaches
+ *                nothing.
+ *   start        mu = mu0, finite everywhere; mu0 == NULL: mu = flow, which must
+ *                then be finite.  Otherwise GQMAP_ERR_INVALID_ARG, before any
+ *                iteration and with the outputs untouched.
+ *   scatter      GQMAP_SCATTER_REFERENCE: legacy/gqmap_cpu.m:58-59 as written
+ *                (a shifted, anti-diffusive sum; with var == NULL and mu0 == NULL
+ *                this is gqmap_cpu_run bit for bit).  GQMAP_SCATTER_ADJOINT: the
+ *                gradient of an edge's second endpoint goes to that endpoint.
+ *                The last row and column own no node term and no edge (the
+ *                reference's loop bounds), so under the adjoint scatter each of
+ *                their nodes hangs on the one edge that ends in it.
+ * Outputs, trace, its_done, sigma0 / seed and the arena as gqmap_cpu_run's.
+ * No reference counterpart. */
+enum { GQMAP_SCATTER_REFERENCE = 0, GQMAP_SCATTER_ADJOINT = 1 };
+gqmap_status gqmap_flow_denoise(const gqmap_cpu_options *o, const double *flow, const double *var,
+                                const double *mu0, int M, int N, const double *sigma0, uint64_t seed,
+                                int scatter, double *mu, double *sigma, double *rou, double *trace,
+                                int *its_done, int device);
+/* The same on device arrays, as gqmap_cpu_run_device: every array is memory of
+ * `device`; host pointers, memory of another device and outputs that overlap
+ * each other or an input (flow, sigma0, var, mu0) are refused.  The start is
+ * checked by one small kernel before anything is written. */
+gqmap_status gqmap_flow_denoise_device(const gqmap_cpu_options *o, const double *flow, const double *var,
+                                       const double *mu0, int M, int N, const double *sigma0, uint64_t seed,
+                                       int scatter, double *mu, double *sigma, double *rou, double *trace,
+                                       int *its_done, int device);
+/* The host model: the same arithmetic in plain C++ (no device; bit-identical),
+ * threaded over columns with a result that does not depend on the thread count
+ * (GQMAP_HOST_THREADS in the environment, default: the hardware's, at most 16). */
+gqmap_status gqmap_flow_denoise_host(const gqmap_cpu_options *o, const double *flow, const double *var,
+                                     const double *mu0, int M, int N, const double *sigma0, uint64_t seed,
+                                     int scatter, double *mu, double *sigma, double *rou, double *trace,
+                                     int *its_done);
+
 /* ---- host helpers (no device needed) ---- */
 /* readFlowFile.m: M x N x 2 (flow == NULL: size query). */
 gqmap_status gqmap_read_flo(const char *path, int *M, int *N, double *flow);
