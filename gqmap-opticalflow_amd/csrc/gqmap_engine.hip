@@ -5079,6 +5079,15 @@ gqmap_status gqmap_debug_read_vv(gqmap_ctx *c, double *out, size_t n, int *store
     return GQMAP_OK;
 }
 
+// Not in the public header (tests): the element type of the context's padded
+// frame -- 0 double, 1 float (vvs_t; every fp32 context that has no pair
+// store), 2 binary16 column pairs (vvh2_t) -- or -1 without images.
+int gqmap_debug_vv_store(const gqmap_ctx *c)
+{
+    if (!c || !c->have_images) return -1;
+    return c->vvp ? 2 : (c->fp32 || c->vv32) ? 1 : 0;
+}
+
 // Not in the public header (tests): 1 when the context's dataflow launches
 // read the offset store (taps by LDS table), 0 when they read the pair store.
 int gqmap_debug_tap_lut(const gqmap_ctx *c) { return c && c->have_images && c->vvp && c->tapt ? 1 : 0; }
