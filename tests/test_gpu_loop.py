@@ -184,7 +184,8 @@ def test_loop_deferred_stop_in_run_timed(k):
 
 
 @pytest.mark.parametrize("engine,L,precision,n_tiles", [("mixture", 3, "fp64", 3), ("mixture", 2, "fp32", 4),
-                                                        ("super", 3, "fp64", 2)])
+                                                        ("super", 3, "fp64", 2), ("mixture", 8, "fp64", 3),
+                                                        ("super", 5, "fp32", 2)])
 def test_loop_exact_step_mixture_components(engine, L, precision, n_tiles):
     """L > 1: every iteration is the exact step (launch_step_rccl: the strip's
     k_iter, the ghost send/recv, the all-gather of the tiles' exact totals,
