@@ -154,6 +154,11 @@ struct RootStaged<float> {
 #define GQ_SCHED_FENCE __builtin_amdgcn_sched_barrier(0)
 #define GQ_PIN64(x) asm volatile("" : "+v"(x))
 #define GQ_PIN_UNIFORM(x) asm volatile("" : "+s"(x))
+#define GQ_PIN_UNIFORM64(x) asm volatile("" : "+s"(x))
+// an element of the padded frame at an integer address (the biased tap view):
+// global memory, so the gather stays a uniform base plus a 32-bit lane offset
+#define GQ_GLOBAL_AS __attribute__((address_space(1)))
+#define GQ_FRAME_WORD_AT(addr) (*(const GQ_GLOBAL_AS uint32_t *)(addr))
 #include "gqmap_math.h"
 
 namespace gq {
@@ -170,6 +175,7 @@ constexpr int TILE = 16;
 constexpr int BLOCK = TILE * TILE;
 constexpr int TS = TAB_STRIDE;
 constexpr int NPLANES = 9;
+static_assert(NPLANES == EDGE_ADDR_PLANES, "edge_addr32_ok bounds a buffer of NPLANES planes");
 constexpr int TRACE_CAP = 8192;
 constexpr int GRAPH_CHUNK = 50;
 // Iterations per launch of a dataflow context (k_iter_flow; chunk_len).  Apart
@@ -313,6 +319,50 @@ __device__ __forceinline__ fix128 wave_sum_fix(fix128 v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += shfl_xor_fix(v, o);
     return v;
+}
+// The wave's sums of three fix128 values by DPP row operations (iter_tile
+// TRIM_FIXSUM_DPP, GQ_FIXSUM_DPP): an inclusive scan inside each row of 16
+// lanes (row_shr 1, 2, 4, 8; a lane without a source adds 0), then row 0's
+// total into row 1 and row 2's into row 3 (row_bcast:15), then lane 31's into
+// rows 2 and 3 (row_bcast:31) -- the totals in lane 63 only, the other lanes
+// hold partial sums.  A 128-bit add is one v_add_co and three v_addc with
+// the DPP modifier on the first source; integer addition modulo 2^128 in
+// another order, so the totals are wave_sum_fix's.  One block of vector
+// instructions: the three values' steps interleaved, so twelve instructions
+// lie between a register's write and its next DPP read (the ISA asks for two
+// wait states, and five between an EXEC write and a DPP operation: the s_nop
+// in front).  All 64 lanes must be active.
+__device__ __forceinline__ void wave_sum_fix3_dpp(fix128 &a, fix128 &b, fix128 &c)
+{
+    unsigned a0 = (unsigned)a, a1 = (unsigned)(a >> 32), a2 = (unsigned)(a >> 64), a3 = (unsigned)(a >> 96);
+    unsigned b0 = (unsigned)b, b1 = (unsigned)(b >> 32), b2 = (unsigned)(b >> 64), b3 = (unsigned)(b >> 96);
+    unsigned c0 = (unsigned)c, c1 = (unsigned)(c >> 32), c2 = (unsigned)(c >> 64), c3 = (unsigned)(c >> 96);
+#define GQ_DPP_ADD128(x0, x1, x2, x3, ctl)                         \
+    "v_add_co_u32_dpp " x0 ", vcc, " x0 ", " x0 " " ctl "\n"       \
+    "v_addc_co_u32_dpp " x1 ", vcc, " x1 ", " x1 ", vcc " ctl "\n" \
+    "v_addc_co_u32_dpp " x2 ", vcc, " x2 ", " x2 ", vcc " ctl "\n" \
+    "v_addc_co_u32_dpp " x3 ", vcc, " x3 ", " x3 ", vcc " ctl "\n"
+#define GQ_DPP_STEP(ctl)                                                                 \
+    GQ_DPP_ADD128("%0", "%1", "%2", "%3", ctl) GQ_DPP_ADD128("%4", "%5", "%6", "%7", ctl) \
+    GQ_DPP_ADD128("%8", "%9", "%10", "%11", ctl)
+    asm volatile("s_nop 4\n"
+                 GQ_DPP_STEP("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0")
+                 GQ_DPP_STEP("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0")
+                 GQ_DPP_STEP("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0")
+                 GQ_DPP_STEP("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0")
+                 GQ_DPP_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf")
+                 GQ_DPP_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
+                 "s_nop 1"
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(c0), "+v"(c1),
+                   "+v"(c2), "+v"(c3)
+                 :
+                 : "vcc");
+#undef GQ_DPP_STEP
+#undef GQ_DPP_ADD128
+    typedef unsigned __int128 u128;
+    a = (fix128)(((u128)a3 << 96) | ((u128)a2 << 64) | ((u128)a1 << 32) | a0);
+    b = (fix128)(((u128)b3 << 96) | ((u128)b2 << 64) | ((u128)b1 << 32) | b0);
+    c = (fix128)(((u128)c3 << 96) | ((u128)c2 << 64) | ((u128)c1 << 32) | c0);
 }
 // The wave's sum of a small count per lane (0 <= v < 64), bit plane by bit
 // plane on the scalar unit: no cross-lane traffic and no vector registers.
@@ -767,7 +817,11 @@ struct EdgeJob {
     bool need;
     R u1, o1, p, o2, u2;
 };
-template <typename R, typename VT, int Q, int TM, int TN, bool COH>
+// A32 (iter_tile TRIM_EDGE_ADDR32, GQ_EDGE_ADDR32): the operands' addresses
+// as the buffer's base plus a 32-bit byte offset, element h + plane MNL with
+// 24-bit multiplies -- for launches the host has checked with edge_addr32_ok
+// (gqmap_math.h); the same loads, in the same order and place.
+template <typename R, typename VT, int Q, int TM, int TN, bool COH, bool A32 = false>
 __device__ __forceinline__ EdgeJob<R> edge_job(const IterParams<R, VT> &P, const R *__restrict__ src, int e,
                                                int tid, int m, int n, int m0, int n0, int64_t loff, bool inner,
                                                bool valid, R mu_u, R mu_v, R sg_u, R sg_v)
@@ -793,6 +847,21 @@ __device__ __forceinline__ EdgeJob<R> edge_job(const IterParams<R, VT> &P, const
     const int64_t MNL = P.MNL;
     const bool r_inner = rm < M && rn < N && node_interior(P, rm, rn);
     jb.need = own_edge ? (inner || (valid && r_inner)) : (hm >= 0 && hn >= 0 && r_inner);
+    if constexpr (A32) {
+      if (jb.need) {
+        const uint32_t uv = (uint32_t)jb.uv, mnl = (uint32_t)MNL;
+        const uint32_t h = edge_elem32(hm, hn, M, (uint32_t)loff);
+        const uint32_t r = edge_elem32(rm, rn, M, (uint32_t)loff);
+        auto at = [&](uint32_t node, uint32_t plane) {
+            return (const R *)((const char *)src + (edge_plane_elem32(node, plane, mnl) * (uint32_t)sizeof(R)));
+        };
+        jb.u1 = own_edge ? (uv ? mu_v : mu_u) : ld_state<COH>(at(h, uv));
+        jb.o1 = own_edge ? (uv ? sg_v : sg_u) : ld_state<COH>(at(h, 2 + uv));
+        jb.p = ld_state<COH>(at(h, 5 + (uint32_t)jb.dir + 2 * uv));  // rou plane 5+e
+        jb.o2 = ld_state<COH>(at(r, 2 + uv));
+        jb.u2 = ld_state<COH>(at(r, uv));
+      }
+    } else
     if (jb.need) {
         const int uv = jb.uv;
         const int64_t h = hm + (int64_t)M * hn + loff;
@@ -966,10 +1035,13 @@ __device__ __forceinline__ void tile_totals_tail(const FinParams &F, int total, 
 
 // Where a tile's node phase reads its taps: the padded frame, and for the
 // offset store (vvo2_t) the LDS table its taps index.
-template <typename R, typename VT>
+// BIAS: the offset store through its biased bases (gqmap_math.h TapViewLutBiased)
+template <bool BIAS = false, typename R, typename VT>
 __device__ __forceinline__ auto tile_frame_view(const IterParams<R, VT> &P, const GQ_LDS_AS double *taplut)
 {
-    if constexpr (is_vvo2<VT>::value) {
+    if constexpr (is_vvo2<VT>::value && BIAS) {
+        return frame_view_lut_biased(P.VV, P.M2, taplut);
+    } else if constexpr (is_vvo2<VT>::value) {
         return frame_view_lut(P.VV, P.M2, taplut);
     } else {
         (void)taplut;
@@ -994,8 +1066,13 @@ __device__ __forceinline__ auto tile_frame_view(const IterParams<R, VT> &P, cons
 // The LDS shares keep their size: wave w owns entries [64 w, 64 w + 64) with
 // row stride grows (the plain form's layout at grows = TM), and every wave
 // of a group runs its tile's halo job itself (5 jobs per wave).
+// TRIM (a sum of the bits below; the fp64 mixture item on the offset store,
+// C2's kernel -- gqmap_tuning.h GQ_TAP_BIAS, GQ_EDGE_ADDR32): integer and
+// copy instructions around the quadrature loops taken out, the arithmetic of
+// gqmap_math.h on the same operands.
+constexpr int TRIM_TAP_BIAS = 1, TRIM_EDGE_ADDR32 = 2, TRIM_FIXSUM_DPP = 4;
 template <typename R, typename VT, int ENG, int Q, bool EDGE_FIRST, bool COH = false, bool NT = false,
-          bool LIT = false, bool GRP = false, int ROTF = GQ_NODE_ROT_OTHER, int HALO = 0>
+          bool LIT = false, bool GRP = false, int ROTF = GQ_NODE_ROT_OTHER, int HALO = 0, int TRIM = 0>
 __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, int it, int parity,
                                           int part_r, TileLdsQ<R, Q> &lds, int l0, int l1, double Tcur,
                                           bool tab_ready, unsigned long long *acc_ring = nullptr,
@@ -1011,6 +1088,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
     // 2 the halo job on another wave in the edge-first workgroups
     static_assert(HALO == 0 || (GRP && sizeof(R) == 8), "the halo forms: the fp64 dataflow item (one component per item)");
     constexpr bool CHAIN = HALO == 1;
+    static_assert(TRIM == 0 || (GRP && ENG == 0 && is_vvo2<VT>::value), "the trimmed item: the fp64 mixture item on the offset store");
     static_assert(!LIT || (ENG == 0 && Q == 1 && sizeof(R) == 8), "literal order: fp64 mixture, Q = 1");
     static_assert(!GRP || (Q == 1 && !LIT), "a tile per wave: one lane per node");
     constexpr bool RS = Q == 0;                       // role split (node / edge waves)
@@ -1119,7 +1197,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         const bool fast = ENG == 0 && __all(!inner || node_unclamped(c, mu_u, mu_v, m, n + P.n_off, P.Mo, P.No,
                                                                      P.gh_xmax, R(ENG == 2 ? CTF_MARGIN : 0.0)));
         if (inner) {
-            const auto fv = tile_frame_view(P, taplut);
+            const auto fv = tile_frame_view<(TRIM & TRIM_TAP_BIAS) != 0>(P, taplut);
             // (at one lane per node only with float taps: the fp64-tap Q = 1
             // kernels would cross 168 VGPRs, 3 -> 2 waves per SIMD)
             constexpr bool PF = QA >= GQ_NODE_PF_MIN_Q && (QA > 1 || sizeof(VT) == 4);
@@ -1154,8 +1232,8 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         // job e+1's operands before computing job e
         constexpr bool PREFETCH = QA >= GQ_PREFETCH_MIN_Q;
         auto job_at = [&](int e) {
-            return edge_job<R, VT, QA, TM, TN, COH>(P, src, e, htid, m, n, m0, n0, MN * l, inner, valid, mu_u, mu_v,
-                                                sg_u, sg_v);
+            return edge_job<R, VT, QA, TM, TN, COH, (TRIM & TRIM_EDGE_ADDR32) != 0>(P, src, e, htid, m, n, m0, n0, MN * l, inner,
+                                                                                    valid, mu_u, mu_v, sg_u, sg_v);
         };
         EdgeJob<R> next{};
         if (PREFETCH) next = job_at(0);
@@ -1255,7 +1333,14 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
                 if (CHAIN && !last) {  // the sums so far to the next wave of the chain
                     if constexpr (CHAIN) halo_chain_pass(hc, halo_tok, cw, lane, hs);
                 } else
-                if (dir == 0) { in_up[uv][0][hb + hr * grows] = g.du2; in_up[uv][1][hb + hr * grows] = g.do2; }
+                if (dir == 0) {
+                    if constexpr ((TRIM & TRIM_EDGE_ADDR32) != 0) {  // (the entry's row offset too by the 24-bit multiply)
+                        const int hrg = (int)__umul24((unsigned)hr, (unsigned)grows);
+                        in_up[uv][0][hb + hrg] = g.du2; in_up[uv][1][hb + hrg] = g.do2;
+                    } else {
+                        in_up[uv][0][hb + hr * grows] = g.du2; in_up[uv][1][hb + hr * grows] = g.do2;
+                    }
+                }
                 else if (hr < grows) { in_left[uv][0][hb + hr] = g.du2; in_left[uv][1][hb + hr] = g.do2; }
             } else if (rtid % QA == 0) {
                 if (dir == 0) { in_up[uv][0][hr * TM] = g.du2; in_up[uv][1][hr * TM] = g.do2; }
@@ -1299,6 +1384,18 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
 
     TL_STAMP(3, __builtin_amdgcn_s_memrealtime());
     // block partials: Energy, sum|dmu_u|, sum|dsigma_u|, #nonfinite, dalpha[0..L-1]
+    if constexpr ((TRIM & TRIM_FIXSUM_DPP) != 0) {
+        // the trimmed item: by DPP, the totals in lane 63 (ENG 0: no AEPE sum)
+        wave_sum_fix3_dpp(fE, fmu, fsg);
+        const fix128 fnf = (fix128)wave_sum_small(nonfinite);
+        if (lane == 63) {
+            red[0][wave] = fE;
+            red[1][wave] = fmu;
+            red[2][wave] = fsg;
+            red[3][wave] = fnf;
+            red[4][wave] = fae;
+        }
+    } else {
     fE = wave_sum_fix(fE);
     fmu = wave_sum_fix(fmu);
     fsg = wave_sum_fix(fsg);
@@ -1310,6 +1407,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         red[2][wave] = fsg;
         red[3][wave] = fnf;
         red[4][wave] = fae;
+    }
     }
     __syncthreads();
     const int NP = NFIX + P.L;
@@ -2106,6 +2204,11 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     constexpr int HALO = !GRP || LIT || W != 0 || sizeof(R) != 8 ? 0
                          : ENG == 0 && is_vvpair<VT>::value ? GQ_FLOW_HALO
                          : ENG == 2 ? GQ_FLOW_HALO_CTF : 0;
+    // the trimmed item (iter_tile TRIM): the same item on the offset store
+    constexpr int TRIM = ENG == 0 && Q == 1 && !LIT && W == 0 && sizeof(R) == 8 && GRP && is_vvo2<VT>::value
+                             ? (GQ_TAP_BIAS ? TRIM_TAP_BIAS : 0) | (GQ_EDGE_ADDR32 ? TRIM_EDGE_ADDR32 : 0) |
+                                   (GQ_FIXSUM_DPP ? TRIM_FIXSUM_DPP : 0)
+                             : 0;
     HaloChain<R> *hc = nullptr;
     if constexpr (HALO == 1) {
         __shared__ HaloChain<R> sh_halo;
@@ -2209,10 +2312,10 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
 #endif
         // (the halo chain's token: this workgroup's claims only grow)
         if (MIX && edge_first)
-            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO, TRIM>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
                                                                                 wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
         else
-            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO, TRIM>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
                                                                                  wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
 #undef GQ_TLW_ARG
         // publish: every wave's stores (state, rou, the slot's sums) are done
@@ -3796,7 +3899,11 @@ bool launch_flow(gqmap_ctx *c, int n, bool dry)
 #if GQ_TAP_LUT
     // taps by LDS table (the offset store, gqmap_set_images); not the
     // 3-wave form of the large frames, which keeps the pair store's kernel
-    if (c->vvp && c->tapt && c->tiles_m * c->tiles_n <= GQ_FLOW_WIDE_ITEMS)
+    // (its edge jobs address the state by 32-bit offsets, GQ_EDGE_ADDR32: a
+    // frame past edge_addr32_ok's bounds keeps the pair store's kernel and
+    // its 64-bit form -- none at this tile count)
+    if (c->vvp && c->tapt && c->tiles_m * c->tiles_n <= GQ_FLOW_WIDE_ITEMS &&
+        (!GQ_EDGE_ADDR32 || edge_addr32_ok(c->M, c->N, c->L, sizeof(double))))
         return !c->lit && c->kq == 1 && launch_flow_q<double, vvo2_t, 0, 1>(c, n, dry);
 #endif
     if (c->vvp) return !c->lit && c->kq == 1 && launch_flow_q<double, vvh2_t, 0, 1>(c, n, dry);

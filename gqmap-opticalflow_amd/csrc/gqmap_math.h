@@ -199,6 +199,22 @@ GQ_HD VP elem_ptr(VP VV, uint32_t elem)
     return byte_ptr(VV, elem * (uint32_t)sizeof(*VV));
 }
 
+// State elements by 32-bit offsets (the trimmed dataflow item's edge jobs,
+// GQ_EDGE_ADDR32): node (m, n) of a component whose first element is loff,
+// then element `node` of plane `plane` of a buffer of NPLANES planes of MNL
+// elements.  Equal to the 64-bit forms m + M n + loff and node + MNL plane
+// where edge_addr32_ok holds: every factor within the 24-bit multiply and the
+// buffer's byte offsets within 32 bits.
+GQ_HD uint32_t edge_elem32(int m, int n, int M, uint32_t loff) { return (uint32_t)m + GQ_UMUL24(M, n) + loff; }
+GQ_HD uint32_t edge_plane_elem32(uint32_t node, uint32_t plane, uint32_t MNL) { return node + GQ_UMUL24(plane, MNL); }
+constexpr int EDGE_ADDR_PLANES = 9;  // planes of a state buffer (the engine's NPLANES)
+constexpr bool edge_addr32_ok(int64_t M, int64_t N, int64_t L, int64_t elem_bytes)
+{
+    constexpr int64_t U24 = (int64_t)1 << 24, U32 = (int64_t)1 << 32;
+    return M >= 0 && N >= 0 && L >= 1 && M < U24 && N < U24 && M * N < U24 && M * N * L < U24 && M * N * L * L < U24 &&
+           EDGE_ADDR_PLANES * (M * N * L) * elem_bytes < U32;
+}
+
 // Paired binary16 storage of the padded frame (policy vv_pair; the fp64
 // single-scale mixture engine on frames whose padded values are all exact in
 // binary16 -- the integer frames of rgb2gray, C2's within [-510, 765]):
@@ -423,6 +439,64 @@ template <typename VP, typename LP>
 GQ_HD TapViewLut<VP, LP> frame_view_lut(VP VV, int M2, LP lut)
 {
     return TapViewLut<VP, LP>{VV, (uint32_t)M2, lut};
+}
+// ... with the address arithmetic of a cell trimmed (iter_tile TRIM_TAP_BIAS,
+// GQ_TAP_BIAS): the base lowered by cell_elem's constant part, the M2 + 1
+// elements of the "- 1"s, so a cell is iy + M2 ix, and the second column pair
+// (+ 2 M2 elements) on a base of its own, so its gather needs no add.  Both
+// bases are integer addresses (cell (1, 1) is the buffer's first element:
+// nothing in front of it is addressed, and no pointer is formed there); an
+// element is read as its 32-bit word through GQ_FRAME_WORD_AT, which an
+// includer may define for another address space.  p: the store itself (its
+// type names the store).
+#ifndef GQ_FRAME_WORD_AT
+GQ_HD uint32_t frame_word_at(uintptr_t addr)
+{
+    uint32_t w;
+    memcpy(&w, (const void *)addr, sizeof w);
+    return w;
+}
+#define GQ_FRAME_WORD_AT(addr) frame_word_at(addr)
+#endif
+GQ_HD uint32_t tap_bias_elems(int M2) { return (uint32_t)M2 + 1u; }
+GQ_HD uint32_t cell_elem_biased(int iy, int ix, int M2) { return (uint32_t)iy + GQ_UMUL24(M2, ix); }
+template <typename VP, typename LP>
+struct TapViewLutBiased {
+    VP p;
+    uint32_t ld;
+    LP lut;
+    uintptr_t b0, b2;  // column pairs 0, 1 / 2, 3 of the cell whose biased index is 0
+    GQ_HD uint32_t cell(int iy, int ix) const { return cell_elem_biased(iy, ix, (int)ld); }
+};
+template <typename VP, typename LP>
+GQ_HD TapViewLutBiased<VP, LP> frame_view_lut_biased(VP VV, int M2, LP lut)
+{
+    constexpr uintptr_t EB = sizeof(*VV);
+    const uintptr_t b0 = (uintptr_t)VV - EB * tap_bias_elems(M2);
+    return TapViewLutBiased<VP, LP>{VV, (uint32_t)M2, lut, b0, b0 + EB * 2u * (uint32_t)M2};
+}
+template <typename T>
+struct is_tap_biased : std::false_type {};
+template <typename VP, typename LP>
+struct is_tap_biased<TapViewLutBiased<VP, LP>> : std::true_type {};
+// The taps of the cell a view's cell() names, in load_taps16's order.
+template <typename TV>
+GQ_HD auto view_taps16(const TV &V, uint32_t o)
+{
+    if constexpr (is_tap_biased<TV>::value) {
+        using E = typename std::remove_cv<typename std::remove_reference<decltype(*V.p)>::type>::type;
+        static_assert(is_vvo2<E>::value && sizeof(E) == 4, "the biased view: the offset store, an element one word");
+        const uint32_t ob = o * 4u;
+        Taps16<E> T;
+        for (int pr = 0; pr < 2; ++pr)
+            for (int r = 0; r < 4; ++r) {
+                const uint32_t w = GQ_FRAME_WORD_AT((pr ? V.b2 : V.b0) + ob + (uint32_t)(4 * r));
+                T.v[4 * pr + r] = E{(uint16_t)(w & 0xffffu), (uint16_t)(w >> 16)};  // (little-endian: lo, hi)
+            }
+        return T;
+    } else {
+        return load_taps16(V.p, o, V.ld);
+    }
 }
 // The sixteen taps of an offset-store cell as their table entries
 // (GQ_LUT_AT), in the column-major order of the plain stores: the values the
@@ -1017,6 +1091,9 @@ constexpr int node_rot_unroll(int rot) { return (rot >> 8) > 1 ? (rot >> 8) : 1;
 #define GQ_PIN64(x) (void)(x)
 #define GQ_PIN_UNIFORM(x) (void)(x)
 #endif
+#ifndef GQ_PIN_UNIFORM64  // (a uniform double)
+#define GQ_PIN_UNIFORM64(x) (void)(x)
+#endif
 template <bool CLAMP, int UNR, typename TP, typename TV, typename IP>
 GQ_HD Sums<double> node_sums_lut(TP tab, int k0, int K2, int dk, const TV &V, IP I1, int Mo, int No, double eps,
                                  const NodeCoef<double> &c, double u1, double u2, int m, int n)
@@ -1033,7 +1110,12 @@ GQ_HD Sums<double> node_sums_lut(TP tab, int k0, int K2, int dk, const TV &V, IP
     };
     const int klast = k0 + (K2 - 1 - k0) / dk * dk;
     double so, to;
-    auto T = load_taps16(V.p, locate(tab[tab_at(T_XI, k0)], tab[tab_at(T_XJ, k0)], so, to), V.ld);
+    auto T = view_taps16(V, locate(tab[tab_at(T_XI, k0)], tab[tab_at(T_XJ, k0)], so, to));
+    // the residual's -1/4: no inline constant, so as a literal the fma is a
+    // destructive v_fmac behind a copy of I; the trimmed item (the biased
+    // view) holds it opaque in a uniform register pair instead
+    double mq = -0.25;
+    if constexpr (is_tap_biased<TV>::value) GQ_PIN_UNIFORM64(mq);
     // the point a trip locates, read from the table a trip ahead (beside the
     // weights of the sums, so the trip's second part does not wait for it)
     const int kn0 = k0 + dk <= klast ? k0 + dk : klast;
@@ -1046,7 +1128,7 @@ GQ_HD Sums<double> node_sums_lut(TP tab, int k0, int K2, int dk, const TV &V, IP
         const Taps16<double> D = lut_taps16(V.lut, T, mask, shift);
         GQ_SCHED_FENCE;
         double sok = so, tok = to;
-        T = load_taps16(V.p, locate(nxi, nxj, so, to), V.ld);  // sample min(k + dk, klast): the last pass reloads its own cell
+        T = view_taps16(V, locate(nxi, nxj, so, to));  // sample min(k + dk, klast): the last pass reloads its own cell
         GQ_SCHED_FENCE;
         // (the fence orders memory operations only: the arithmetic of the
         // third part starts from here)
@@ -1055,7 +1137,7 @@ GQ_HD Sums<double> node_sums_lut(TP tab, int k0, int K2, int dk, const TV &V, IP
         const int kn2 = k + 2 * dk <= klast ? k + 2 * dk : klast;
         nxi = tab[tab_at(T_XI, kn2)];
         nxj = tab[tab_at(T_XJ, kn2)];
-        const double d = fma(bicubic_taps4<double>(D, sok, tok), -0.25, I);
+        const double d = fma(bicubic_taps4<double>(D, sok, tok), mq, I);
         S.add(tab, k, GQ_SQRT(fma(d, d, eps)));
         // (the sums, and the wait for their weights, before the next trip's
         // table reads: those then have the position arithmetic to run behind)

@@ -130,6 +130,32 @@
 #ifndef GQ_TAP_LUT
 #define GQ_TAP_LUT 1
 #endif
+// Address arithmetic, copies and cross-lane traffic around the quadrature
+// loops of that item (iter_tile TRIM; the floating-point instructions are
+// gqmap_math.h's and stay; every other instantiation keeps its code).
+// profiles/item_trim_ab.txt: the first two together C2 fp64 -0.9 / -0.6% in
+// two sessions (each alone +0.2 / +0.3%: inside the spread), all three
+// -1.7 / -2.5% in two sessions, every round ahead; DESIGN.md 4, 8.
+// GQ_TAP_BIAS: the node loop's tap bases lowered by the constant part of a
+// cell's index, the second column pair on a base of its own, and the
+// residual's -1/4 in a uniform register pair (TapViewLutBiased): 87 -> 84
+// VALU per sample.
+// GQ_EDGE_ADDR32: the edge jobs' operand loads at the state buffer's base
+// plus a 32-bit element offset (edge_job; the host takes this kernel only
+// where edge_addr32_ok holds, the pair store's kernel otherwise): no 64-bit
+// multiplies in the job loop.
+// GQ_FIXSUM_DPP: the item's three exact partial sums reduced over a wave by
+// DPP row operations with carry chains (wave_sum_fix3_dpp: 72 VALU, no LDS;
+// the totals in lane 63) in place of the ds_bpermute butterfly.
+#ifndef GQ_TAP_BIAS
+#define GQ_TAP_BIAS 1
+#endif
+#ifndef GQ_EDGE_ADDR32
+#define GQ_EDGE_ADDR32 1
+#endif
+#ifndef GQ_FIXSUM_DPP
+#define GQ_FIXSUM_DPP 1
+#endif
 #ifndef GQ_UNROLL_MIN_Q
 #define GQ_UNROLL_MIN_Q 2
 #endif
