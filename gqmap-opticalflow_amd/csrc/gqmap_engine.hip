@@ -188,9 +188,6 @@ constexpr int GRAPH_CHUNK = 50;
 // 250 is the smallest launch of the fit at which that is under 0.5% of the
 // launch.  A failed launch is re-run from its snapshot with one launch per
 // iteration, so up to FLOW_CHUNK iterations are repeated.
-#ifndef GQ_FLOW_CHUNK
-#define GQ_FLOW_CHUNK 250
-#endif
 constexpr int FLOW_CHUNK = GQ_FLOW_CHUNK;
 static_assert(FLOW_CHUNK >= 1 && FLOW_CHUNK <= TRACE_CAP, "a launch's trace rows fit the ring");
 constexpr int NFIX = 5;        // fixed slots per block: Energy, sum|dmu_u|, sum|dsig_u|, #nonfinite, AEPE sum
@@ -218,9 +215,7 @@ struct Ctl {
     // has judged the stop rule on the all-gathered totals.  A cache line of
     // their own.  ovr: 1 + the sequence row whose totals met the stop rule
     // when later iterations of the sequence had already run (the host then
-    // restores the sequence's snapshot and re-runs it exactly, ovr_recover);
-    // also 1 + the launch-local stop iteration of a dataflow launch whose
-    // items ran two or more iterations past it (GQ_FLOW_LAG > 2).
+    // restores the sequence's snapshot and re-runs it exactly, ovr_recover).
     alignas(128) int it_i;
     int done_i;
     double T_i;
@@ -429,11 +424,12 @@ __device__ __forceinline__ Sums<float> edge_sums_pk(TP tab, int k0, int K2, int 
     return S;
 }
 
-// PU: mirror pairs per loop trip (0: GQ_PAIR_UNROLL_N)
+// PU: mirror pairs per loop trip (0: GQ_PAIR_UNROLL_N); fp32 sums the pairs
+// on packed float2 registers (profiles/r02_lane_mask_pk.txt)
 template <int PU = 0, typename R, typename TP>
 __device__ __forceinline__ Sums<R> edge_sums_dev(TP tab, int k0, int K2, int dk, R eps, const EdgeCoef<R> &c)
 {
-    if constexpr (sizeof(R) == 4 && GQ_EDGE_PK)
+    if constexpr (sizeof(R) == 4)
         return edge_sums_pk<PU>(tab, k0, K2, dk, eps, c);
     else
         return edge_sums<PU>(tab, k0, K2, dk, eps, c);
@@ -546,7 +542,6 @@ __device__ void fin_reduce(const FinParams &F, double *tot, fix128 *sh)
     auto row_val = [&](int r, int q) -> fix128 {
         return gathered ? F.gathered[(int64_t)r * NP + q] : load_part_agent(F.partials, F.nblocks, r, q);
     };
-#if GQ_FIN_GROUP
     {   // the NFIX fixed quantities of FIN_ROWS rows per thread together: all
         // their (device-coherent, high-latency) loads in flight at once
         constexpr int FIN_ROWS = 4;
@@ -569,9 +564,6 @@ __device__ void fin_reduce(const FinParams &F, double *tot, fix128 *sh)
         }
     }
     for (int q = NFIX; q < NPR; ++q) {
-#else
-    for (int q = 0; q < NPR; ++q) {
-#endif
         fix128 v = 0;
         for (int r0 = tid; r0 < rows; r0 += 4 * 256) {
             fix128 x[4];
@@ -657,18 +649,12 @@ __device__ void fin_apply(const FinParams &F, const double *tot)
 // combine with an xor butterfly (the spec's butterfly()).
 // ---------------------------------------------------------------------------
 // Waves per SIMD the register allocation must allow (MI355X: 136-168 VGPRs
-// -> 3, 176-256 -> 2, more -> 1).  Left to the allocator: forcing 3 waves on
-// the single-scale engine moved arrays to scratch (C2 +24%); bounding the
-// super engine to 2 made its block sum 25% slower than the allocator's own
-// 2-wave (<= 256 VGPR) schedule.  GQ_MIN_WAVES / GQ_SUPER_WAVES: experiments.
-// smallest lanes-per-node split whose edge jobs prefetch the next job's
-// operands / run fully unrolled (experiments: GQ_PREFETCH_MIN_Q, GQ_UNROLL_MIN_Q)
-constexpr int min_waves(int eng, int q)
-{
-    return GQ_MIN_WAVES > 1 ? GQ_MIN_WAVES
-         : eng == 1        ? GQ_SUPER_WAVES
-         : (q >= 2 && q <= 8) ? GQ_MIDQ_WAVES : 1;
-}
+// -> 3, 176-256 -> 2, more -> 1): the per-launch kernels leave it to the
+// allocator (launch bound 1).  Forcing 3 waves on the single-scale engine
+// moved arrays to scratch (C2 +24%); bounding the super engine to 2 made its
+// block sum 25% slower than the allocator's own 2-wave (<= 256 VGPR)
+// schedule; a 3-wave bound on the Q = 2, 4, 8 levels lost too
+// (profiles/r02_split_sweep.txt, r05_level_variants.txt).
 
 // Tile index of block b: XCD-aware order.  Blocks b and b+8 share an XCD
 // (round-robin dispatch), so each XCD gets a contiguous band of tiles (L2
@@ -753,7 +739,7 @@ struct TileLds {
     R nd[RS ? 7 : 1][RS ? TPIX : 1];
 };
 template <typename R, int Q>
-using TileLdsQ = TileLds<R, tile_pix(Q), (Q > 1 && GQ_TAB_LDS), Q == 0>;
+using TileLdsQ = TileLds<R, tile_pix(Q), (Q > 1), Q == 0>;
 
 #if GQ_TIMELINE
 // debug builds: per-block stamps (s_memrealtime, 100 MHz) of k_iter
@@ -874,10 +860,6 @@ __device__ __forceinline__ EdgeJob<R> edge_job(const IterParams<R, VT> &P, const
     }
     return jb;
 }
-
-#ifndef GQ_FLOW_TL  // diagnostic builds: the dataflow launch's timeline (k_iter_flow)
-#define GQ_FLOW_TL 0
-#endif
 
 // The halo chain of the plain dataflow item (iter_tile HALO == 1, DESIGN.md
 // 4): the halo job's pair range in four ascending slices, wave w running
@@ -1085,7 +1067,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
 {
     // HALO (the plain form of GRP, !grouped; GQ_FLOW_HALO in gqmap_tuning.h):
     // 1 the halo job handed round the four waves (hc, halo_tok: HaloChain),
-    // 2 the halo job on another wave in the edge-first workgroups
+    // 0 wave 0 runs it as a fifth job
     static_assert(HALO == 0 || (GRP && sizeof(R) == 8), "the halo forms: the fp64 dataflow item (one component per item)");
     constexpr bool CHAIN = HALO == 1;
     static_assert(TRIM == 0 || (GRP && ENG == 0 && is_vvo2<VT>::value), "the trimmed item: the fp64 mixture item on the offset store");
@@ -1123,7 +1105,7 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
     const bool inner = valid && node_interior(P, m, n);
     const bool lead = kj == 0;  // the lane that owns the node's outputs
     const int K2 = P.K2;
-    constexpr bool TAB_LDS = QA > 1 && GQ_TAB_LDS;
+    constexpr bool TAB_LDS = QA > 1;  // lane-varying indices: the table staged in LDS
     using tab_t = std::conditional_t<TAB_LDS, const R *, ctab_t<R>>;
     tab_t tab;
     if constexpr (TAB_LDS) {
@@ -1150,7 +1132,6 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
     int htid = rtid;  // the halo edge a lane computes
     if constexpr (GRP) {
         if (grouped) halo_lane = tile >= 0;
-        else if (HALO == 2 && EDGE_FIRST) halo_lane = wave == GQ_FLOW_HALO_ROT_WAVE;
         htid = lane;
     }
     // the chain runs in the items whose four waves share one tile
@@ -1198,9 +1179,10 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
                                                                      P.gh_xmax, R(ENG == 2 ? CTF_MARGIN : 0.0)));
         if (inner) {
             const auto fv = tile_frame_view<(TRIM & TRIM_TAP_BIAS) != 0>(P, taplut);
-            // (at one lane per node only with float taps: the fp64-tap Q = 1
-            // kernels would cross 168 VGPRs, 3 -> 2 waves per SIMD)
-            constexpr bool PF = QA >= GQ_NODE_PF_MIN_Q && (QA > 1 || sizeof(VT) == 4);
+            // software-pipelined (profiles/r05_node_pf_ab.txt; at one lane per
+            // node only with float taps: the fp64-tap Q = 1 kernels would
+            // cross 168 VGPRs, 3 -> 2 waves per SIMD)
+            constexpr bool PF = QA > 1 || sizeof(VT) == 4;
             // the pipelined loop's form (node_sums ROT: rotation, trips per
             // pass), chosen by the kernel that instantiates the tile (ROTF)
             constexpr int ROT = PF ? ROTF : 0;
@@ -1228,19 +1210,20 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
         // lanes, and a node's lanes are all halo lanes or none (asserted).
         static_assert(HALO_LANES % QA == 0, "a node's lanes share their job count");
         const int njobs = halo_lane || chain ? 5 : 4;
-        // Q >= 4 (small grids, about one wave per SIMD: latency-bound) loads
-        // job e+1's operands before computing job e
-        constexpr bool PREFETCH = QA >= GQ_PREFETCH_MIN_Q;
+        // two or more lanes per node (small grids, about one wave per SIMD:
+        // latency-bound) load job e+1's operands before computing job e
+        // (profiles/r02_edge_prefetch_ab.txt)
+        constexpr bool PREFETCH = QA >= 2;
         auto job_at = [&](int e) {
             return edge_job<R, VT, QA, TM, TN, COH, (TRIM & TRIM_EDGE_ADDR32) != 0>(P, src, e, htid, m, n, m0, n0, MN * l, inner,
                                                                                     valid, mu_u, mu_v, sg_u, sg_v);
         };
         EdgeJob<R> next{};
         if (PREFETCH) next = job_at(0);
-        // Q >= 4 single-pixel engines: a constant trip count, fully unrolled
+        // ... and on the single-pixel engines: a constant trip count, fully unrolled
         // (independent jobs overlap; ctf 30x40 30.0 -> 28.8 us/it; not the
         // super engine, which it would push past 256 VGPRs: C4 355 -> 407)
-        constexpr bool JOBS_UNROLLED = QA >= GQ_UNROLL_MIN_Q && ENG != 1;
+        constexpr bool JOBS_UNROLLED = QA >= 2 && ENG != 1;
         constexpr int JOB_UNROLL = JOBS_UNROLLED ? 5 : 1;
         static_assert(!CHAIN || (!PREFETCH && !JOBS_UNROLLED), "the chain: one job body, streamed");
 #pragma unroll JOB_UNROLL
@@ -1454,8 +1437,8 @@ __device__ __forceinline__ void k_iter_body(const IterParams<R, VT> &P)
     // edge, node first; the ctf levels at Q = 1 edge, node, edge: 480x640
     // -2.7%, against +4.6% on C2 and +34% on C2 fp32, profiles/r05_phase_mix_inv.txt).
     // Not for the super engine, whose node phase dominates (C4: 850 vs 680 us/it).
-    constexpr int INV = ENG == 2 && Q == 1 ? GQ_PHASE_MIX_CTF_Q1_INV : GQ_PHASE_MIX_OTHER_INV;
-    const bool edge_first = GQ_PHASE_MIX && ENG != 1 && ((((b >> 3) / P.cu_slots) & 1) != INV);
+    constexpr int INV = ENG == 2 && Q == 1;
+    const bool edge_first = ENG != 1 && ((((b >> 3) / P.cu_slots) & 1) != INV);
     __shared__ TileLdsQ<R, Q> lds;
     const int part_r = P.part_off + b;
     if (idle) {
@@ -1516,16 +1499,13 @@ __device__ __forceinline__ void k_iter_body(const IterParams<R, VT> &P)
 }
 
 template <typename R, typename VT, int ENG, int Q, bool NT = false>
-__global__ __launch_bounds__(BLOCK, min_waves(ENG, Q)) void k_iter(IterParams<R, VT> P)
+__global__ __launch_bounds__(BLOCK, 1) void k_iter(IterParams<R, VT> P)
 {
     k_iter_body<R, VT, ENG, Q, NT>(P);
 }
 
 // The literal-order arithmetic (gqmap_options.arith = GQMAP_ARITH_LITERAL):
 // the same tiles, halo, update and finalize with lit_node_grad / lit_edge_grad.
-#ifndef GQ_LIT_WAVES  // waves per SIMD the literal kernel's allocation must allow (1: the allocator's choice)
-#define GQ_LIT_WAVES 3
-#endif
 template <typename VT, bool NT = false>
 __global__ __launch_bounds__(BLOCK, GQ_LIT_WAVES) void k_iter_lit(IterParams<double, VT> P)
 {
@@ -1834,7 +1814,7 @@ __device__ void pfin_reduce(const FinParams &F, int row0, int rows, double *tot,
 }
 
 template <typename R, typename VT, int ENG, int Q>
-__global__ __launch_bounds__(Q == 64 ? WN_THREADS : BLOCK, Q == 64 ? 1 : min_waves(ENG, Q))
+__global__ __launch_bounds__(Q == 64 ? WN_THREADS : BLOCK, 1)
 void k_iter_persist(IterParams<R, VT> P, int n_iter)
 {
     Ctl *ctl = P.ctl;
@@ -1870,7 +1850,7 @@ void k_iter_persist(IterParams<R, VT> P, int n_iter)
         return;
     }
     const int tile = tile_of_block(b, G, Q == 64 ? 1 : P.cu_group, P.cu_slots);
-    const bool edge_first = GQ_PHASE_MIX && Q != 64 && (((b >> 3) / P.cu_slots) & 1);
+    const bool edge_first = Q != 64 && (((b >> 3) / P.cu_slots) & 1);
     for (int j = 0; j < n_iter; ++j) {
         if (j > 0 && !pbar_wait(bar, j - 1, nblk, &sh_flag)) break;
         const int it = it0 + j, parity = (done0 + j) & 1, part_r = ((j & 1) * G) + b;
@@ -1894,8 +1874,7 @@ void k_iter_persist(IterParams<R, VT> P, int n_iter)
 // Before every persistent / dataflow launch: the state it starts from (the
 // current ping-pong buffer and Ctl), unless a launch has already failed or
 // the run has stopped -- then the snapshot of the failed (or stopping)
-// launch's start is kept for the host to restore (persist_recover,
-// ovr_recover).
+// launch's start is kept for the host to restore (persist_recover).
 template <typename R>
 __global__ __launch_bounds__(256) void k_persist_snap(const Ctl *ctl, const unsigned *bar, const R *st0, const R *st1,
                                                       R *snap, Ctl *snap_ctl, int64_t n)
@@ -1937,7 +1916,7 @@ __global__ __launch_bounds__(256) void k_persist_snap(const Ctl *ctl, const unsi
 // j - 1 (finished) or the finalize of j - 2 (every item of j - 2 has
 // arrived).  The progress condition is therefore one running workgroup per
 // XCD queue (the grid is at least 8 workgroups, blockIdx & 7 the queue), not
-// a resident grid.  A group of partial tiles (GQ_FLOW_GROUPS) is one queue
+// a resident grid.  A group of partial tiles is one queue
 // item holding up to four tiles that follow each other in the band's walk:
 // it waits for the union of its members' dependencies -- members' own and
 // their neighbours' iteration j - 1, all of them earlier in the same queue's
@@ -1949,7 +1928,7 @@ __global__ __launch_bounds__(256) void k_persist_snap(const Ctl *ctl, const unsi
 // snapshot and goes on with one launch per iteration (persist_recover).
 //
 // Totals: each tile adds its exact sums into the accumulator slot of its
-// iteration (j % GQ_FLOW_LAG); the tile arriving last for iteration j waits for
+// iteration (j % 2); the tile arriving last for iteration j waits for
 // finalize(j - 1), then reduces the slot and runs fin_apply (acquire and
 // release fences around it: the previous finalizer may have run on another
 // XCD) and publishes the finalized count.  The stop rule: finalize(s) stores
@@ -1961,35 +1940,27 @@ __global__ __launch_bounds__(256) void k_persist_snap(const Ctl *ctl, const unsi
 // leaves them.  State moves between workgroups through device-coherent
 // (agent-scope) loads and stores (ld_state / st_state).
 // ---------------------------------------------------------------------------
-// GQ_FLOW_LAG: iterations an item may run ahead of the finalize -- item j
-// starts once iterations up to j - GQ_FLOW_LAG are finalized.  2 (kept): the
-// buffer an item writes never holds a state that may have met the stop
-// rule.  Deeper (a diagnostic): an item of iteration s + 2 may overwrite the
-// buffer of a state s that met it; the launch then records the overshoot
-// (Ctl::ovr) and the host restores the chunk's snapshot and re-runs up to s
-// with one launch per iteration (ovr_recover).  The timeline of the lag-2
-// form shows items waiting 24% of their time; lags 4, 6 and 8 left both the
-// wait (lag 6: 24%) and C2 / the C3 levels unchanged within 1%
-// (profiles/r06_flow_lag_ab.txt, r06_flow_timeline_lag{2,6}.txt): the wait
-// is the neighbour dependencies -- a band of 116 tiles per XCD against 96
-// resident slots leaves about 1.2 item-times between an item's claim and
-// its neighbours' claims of the previous iteration -- not the finalize.
-#ifndef GQ_FLOW_LAG
-#define GQ_FLOW_LAG 2
-#endif
-constexpr int FL_SLOTS = GQ_FLOW_LAG;              // accumulator / ticket slots (iteration j: j % FL_SLOTS)
+// An item runs at most two iterations ahead of the finalize -- item j starts
+// once iterations up to j - 2 are finalized: the buffer an item writes never
+// holds a state that may have met the stop rule.  The timeline shows items
+// waiting 24% of their time; deeper lags (4, 6, 8) left both the wait and
+// C2 / the C3 levels unchanged within 1% (profiles/r06_flow_lag_ab.txt,
+// r06_flow_timeline_lag{2,6}.txt): the wait is the neighbour dependencies --
+// a band of 116 tiles per XCD against 96 resident slots leaves about 1.2
+// item-times between an item's claim and its neighbours' claims of the
+// previous iteration -- not the finalize.
+constexpr int FL_SLOTS = 2;                        // accumulator / ticket slots (iteration j: j % FL_SLOTS)
 constexpr int FL_LINE = 32;                        // 32-bit words per 128-byte line
 constexpr int FL_Q = 0;                            // 8 per-XCD claim counters, a line each
 constexpr int FL_FIN = 8 * FL_LINE;                // iterations finalized (launch-local)
 constexpr int FL_STOP = 9 * FL_LINE;               // 1 + the launch-local iteration that stopped the run
 constexpr int FL_EXIT = 10 * FL_LINE;              // workgroups that have left
-constexpr int FL_MAXJ = 11 * FL_LINE;              // 1 + the largest iteration an item started
+// (line 11 is reserved: the offsets below are part of every k_iter_flow)
 constexpr int FL_ARR = 12 * FL_LINE;               // arrival tickets of the slots (a line each)
 constexpr int FL_ACC = FL_ARR + FL_SLOTS * FL_LINE;  // the slots' ACC_SLICES x (NFIX + LMAX) x 4 u64 limbs
 constexpr int FL_ACC_SLOT = ACC_SLICES * (NFIX + GQMAP_LMAX) * 4;  // u64 per slot
 constexpr int FL_DONE = FL_ACC + 2 * FL_SLOTS * FL_ACC_SLOT;       // per tile: iterations done (launch-local)
 constexpr int flow_words(int ntiles) { return FL_DONE + ntiles; }
-static_assert(FL_SLOTS >= 2, "the finalize lag is at least 2");
 static_assert((FL_ACC & 1) == 0, "u64 alignment of the accumulator slots");
 
 // Wait (wave 0 polls, the workgroup follows) until item (j, tile) may run.
@@ -2123,48 +2094,26 @@ __device__ unsigned long long g_flow_tlw[4 * FLOW_TL_WORDS];
 // of 116 tiles ~64 items in flight -- more slack for the neighbour
 // dependencies; C2 fp64 142.9 -> 139.6 us/it (graph), the 480x640 ctf level
 // ~278 -> ~275 (profiles/r06_flow_2waves_ab.txt, same checksums).
-#ifndef GQ_FLOW_WAVES
-#define GQ_FLOW_WAVES 2
-#endif
-#ifndef GQ_FLOW_LIT_WAVES  // the same for the literal-order instantiation (2: <= 256 VGPRs, no spills)
-#define GQ_FLOW_LIT_WAVES 2
-#endif
-#ifndef GQ_FLOW_MIX  // node-first / edge-first alternation among co-resident workgroups
-#define GQ_FLOW_MIX 1
-#endif
-#ifndef GQ_FLOW_LIT_MIX
-#define GQ_FLOW_LIT_MIX 0
-#endif
-#ifndef GQ_FLOW_COH  // device-coherent state access (0: plain -- timing experiments only, not coherent)
-#define GQ_FLOW_COH 1
-#endif
-#ifndef GQ_FLOW_PREFETCH  // claim the next item while the current one runs (measured: +18%, reservation skew)
-#define GQ_FLOW_PREFETCH 0
-#endif
-#ifndef GQ_FLOW_PAIR  // the next claim issued together with the arrival ticket (one round trip)
-#define GQ_FLOW_PAIR 0
-#endif
+// (GQ_FLOW_WAVES; GQ_FLOW_LIT_WAVES the same for the literal-order
+// instantiation: <= 256 VGPRs, no spills.)  State access is device-coherent
+// (iter_tile COH): items of one iteration run on different XCDs, and plain
+// loads gave other results (profiles/r06_flow_variants.txt).
 // Each XCD queue walks its band row by row (band_row_tile) instead of down
 // the tile columns: a tile's left / right neighbours are then one queue
 // position away instead of a tile column (C2: 25 positions), so the items
 // of iteration j + 1 rarely find a neighbour of iteration j still running
-// (about 96 items are in flight per XCD against a band of 116).
-#ifndef GQ_FLOW_ROWS
-#define GQ_FLOW_ROWS 1
-#endif
+// (about 96 items are in flight per XCD against a band of 116;
+// profiles/r06_flow_rows_ab.txt).
 // Partial tiles of the last tile row grouped by up to four into one item, a
 // tile per wave (k_iter_flow, iter_tile's GRP form).  C2's 388 node rows
 // leave a 25th tile row of 4: its 37 tiles held a slot for a full item time
 // each with 16 of 64 lanes live; grouped they are 13 items (a group stays
 // inside its band: 8 groups of four and 5 single tiles), 925 -> 901 items
 // per iteration (profiles/flow_groups_chunk_ab.txt: -2.2 to -2.6%).
-#ifndef GQ_FLOW_GROUPS
-#define GQ_FLOW_GROUPS 1
-#endif
 // W > 0: the waves per SIMD, overriding the defaults above (the large-frame
 // instantiation, launch_flow_q)
 template <typename R, typename VT, int ENG, int Q, bool LIT = false, int W = 0>
-__global__ __launch_bounds__(BLOCK, W > 0 ? W : LIT ? GQ_FLOW_LIT_WAVES : Q == 1 ? GQ_FLOW_WAVES : ENG == 1 ? 2 : min_waves(ENG, Q))
+__global__ __launch_bounds__(BLOCK, W > 0 ? W : LIT ? GQ_FLOW_LIT_WAVES : Q == 1 ? GQ_FLOW_WAVES : ENG == 1 ? 2 : 1)
 void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, const Ctl *snap)
 {
     static_assert(Q >= 1 && Q <= 4, "1..4 lanes per node");
@@ -2186,12 +2135,12 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     // engine (its node grid is small; a tile's components run back to back
     // in the queue), one otherwise (L = 1)
     const int L = ENG == 1 ? P.L : 1, nitems = ntiles * L;
-    // Groups (GQ_FLOW_GROUPS; the fast arithmetic at one lane per node): when
+    // Groups (the fast arithmetic at one lane per node): when
     // the last tile row holds vr <= 4 node rows, a tile's valid nodes fit in
     // one wave, and up to four of its tiles that follow each other in the
     // band's row walk -- the band's nlast last positions -- are one item:
     // wave w runs member w.  nbl: the band's items per iteration.
-    constexpr bool GRP = GQ_FLOW_GROUPS && Q == 1 && !LIT && (ENG == 0 || ENG == 2);
+    constexpr bool GRP = Q == 1 && !LIT && (ENG == 0 || ENG == 2);
     // form of the node loop (node_sums ROT): the fp64 mixture item on the
     // binary16 pair store at its own register allocation (C2's kernel; not
     // the 3-wave large-frame form, not the float store: not measured)
@@ -2229,13 +2178,13 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
         taplut = (const GQ_LDS_AS double *)sh_taplut;
     }
     const int vr = P.M - (P.tiles_m - 1) * tile_rows(Q);
-    const bool groups = GRP && GQ_FLOW_ROWS && vr <= 4;
+    const bool groups = GRP && vr <= 4;
     const int nlast = groups ? (s0 + nb) / P.tiles_m - s0 / P.tiles_m : 0;  // the band's tiles in the last tile row
     const int nbl = groups ? nb - nlast + ((nlast + 3) >> 2) : nb * L;
-    constexpr int INV = ENG == 2 && Q == 1 ? GQ_PHASE_MIX_CTF_Q1_INV : GQ_PHASE_MIX_OTHER_INV;
-    // (the phase mix: the fast mixture engine; the literal kernel's with
-    // GQ_FLOW_LIT_MIX -- its second instantiation spilled at 3 waves)
-    constexpr bool MIX = GQ_FLOW_MIX && ENG == 0 && (!LIT || GQ_FLOW_LIT_MIX);
+    constexpr int INV = ENG == 2 && Q == 1;
+    // (the phase mix: the fast mixture engine only -- the literal kernel's
+    // second instantiation spilled at 3 waves; profiles/r06_mix_fp32flow_ab.txt)
+    constexpr bool MIX = ENG == 0 && !LIT;
     const bool edge_first = MIX && ((((b >> 3) / P.cu_slots) & 1) != INV);
     __shared__ TileLdsQ<R, Q> lds;
     __shared__ int sh_i, sh_go, sh_last;
@@ -2244,21 +2193,11 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     __shared__ unsigned long long sh_acc[4 * (NFIX + GQMAP_LMAX)];
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(fl + FL_ACC);
     unsigned *q = fl + FL_Q + xcd * FL_LINE;
-    unsigned nxt = 0;  // thread 0: the claim issued during the previous item
-    if (run && nb > 0 && GQ_FLOW_PREFETCH && threadIdx.x == 0)
-        nxt = __hip_atomic_fetch_add(q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    bool have = false;  // GQ_FLOW_PAIR: sh_i already holds the next claim
     while (run && nb > 0) {
-        if (threadIdx.x == 0 && !(GQ_FLOW_PAIR && have)) {
-            if (GQ_FLOW_PREFETCH) {
-                sh_i = (int)nxt;
-                // the next claim goes out now; its latency hides behind this
-                // item's first state loads (a claim past the last item is harmless)
-                if ((int)nxt / nbl < n_iter) nxt = __hip_atomic_fetch_add(q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                sh_i = (int)__hip_atomic_fetch_add(q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        // the claim, when the previous item is done (claiming the next item
+        // while this one runs skewed the queues: +18%, profiles/r06_flow_variants.txt;
+        // with the arrival ticket: neutral, r06_flow_prefetch_pair_2waves_ab.txt)
+        if (threadIdx.x == 0) sh_i = (int)__hip_atomic_fetch_add(q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         const int i = sh_i, j = i / nbl, l = ENG == 1 ? i % L : 0;
         if (j >= n_iter) break;
@@ -2268,7 +2207,7 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
             pos = nb - nlast + 4 * (pos - (nb - nlast));
             gsize = min(4, nb - pos);
         }
-        const int tile = GQ_FLOW_ROWS ? band_row_tile(pos, s0, s0 + nb, P.tiles_m) : s0 + pos;
+        const int tile = band_row_tile(pos, s0, s0 + nb, P.tiles_m);
         if constexpr (GRP) {  // the member tiles (the previous item's readers are past its last barrier)
             if (threadIdx.x < 4)
                 sh_grp[threadIdx.x] = threadIdx.x == 0 ? tile
@@ -2281,11 +2220,9 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
 #if GQ_FLOW_TL
         const unsigned long long tl_claim = __builtin_amdgcn_s_memrealtime();
 #endif
-        if (!flow_wait(fl, bar, P.tiles_m, ntiles, tile, l, L, j, alpha_moved ? j : j - GQ_FLOW_LAG + 1, &sh_go,
+        if (!flow_wait(fl, bar, P.tiles_m, ntiles, tile, l, L, j, alpha_moved ? j : j - 1, &sh_go,
                        GRP && grouped ? sh_grp : nullptr))
             break;
-        if (GQ_FLOW_LAG > 2 && threadIdx.x == 0)  // (for the overshoot check at the exit)
-            __hip_atomic_fetch_max(fl + FL_MAXJ, (unsigned)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #if GQ_FLOW_TL
         const unsigned long long tl_go = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -2312,11 +2249,11 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
 #endif
         // (the halo chain's token: this workgroup's claims only grow)
         if (MIX && edge_first)
-            iter_tile<R, VT, ENG, Q, true, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO, TRIM>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
-                                                                                wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
+            iter_tile<R, VT, ENG, Q, true, true, false, LIT, GRP, ROTF, HALO, TRIM>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+                                                                                    wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
         else
-            iter_tile<R, VT, ENG, Q, false, GQ_FLOW_COH, false, LIT, GRP, ROTF, HALO, TRIM>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
-                                                                                 wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
+            iter_tile<R, VT, ENG, Q, false, true, false, LIT, GRP, ROTF, HALO, TRIM>(P, wtile, it, parity, 0, lds, l0, l1, T, false, slot,
+                                                                                     wrows, grouped, hc, (unsigned)i + 1, taplut GQ_TLW_ARG);
 #undef GQ_TLW_ARG
         // publish: every wave's stores (state, rou, the slot's sums) are done
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2339,10 +2276,8 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
             __hip_atomic_store(fl + FL_DONE + tile * L + l, (unsigned)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned tk = __hip_atomic_fetch_add(fl + FL_ARR + (j % FL_SLOTS) * FL_LINE, (unsigned)gsize, __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_AGENT);
-            if (GQ_FLOW_PAIR) sh_i = (int)__hip_atomic_fetch_add(q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             sh_last = tk == (unsigned)(nitems - gsize);
         }
-        have = true;
         __syncthreads();
         if (sh_last) flow_finalize(P.fin, fl, bar, slot, j, tot, sh_acc, &sh_go);
         __syncthreads();
@@ -2353,14 +2288,7 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
         sh_last = __hip_atomic_fetch_add(fl + FL_EXIT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
     __syncthreads();
     if (sh_last) {
-        if (threadIdx.x == 0 && GQ_FLOW_LAG > 2) {
-            // an item of iteration >= s + 2 ran after the stop at s: the
-            // buffer of state s may be overwritten -- the host recovers
-            const unsigned st = __hip_atomic_load(fl + FL_STOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned mj = __hip_atomic_load(fl + FL_MAXJ, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (st != 0 && mj >= st + 2) __hip_atomic_store(&P.ctl->ovr, (int)st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
+        __syncthreads();  // (a second barrier nothing needs: it stays so that the kernels' code does not move)
         for (int w = threadIdx.x; w < flow_words(nitems); w += blockDim.x)
             __hip_atomic_store(fl + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -2715,7 +2643,7 @@ struct Policy {
     int flow = -1;         // dataflow launch (k_iter_flow): -1 auto (fp64 whole grids at Q = 1, 2), 0 off, 1 on
     int vv_float = 1;      // float padded-frame store when exact
     int vv_pair = 1;       // binary16 column-pair store when exact (fp64 single-scale mixture, Q = 1)
-    int tap_lut = 1;       // offset store beside it, taps by LDS table (fp64 dataflow item; GQ_TAP_LUT)
+    int tap_lut = 1;       // offset store beside it, taps by LDS table (fp64 dataflow item)
     int verbose = 0;       // recovery messages on stderr
 };
 Policy g_pol;
@@ -3242,11 +3170,7 @@ bool launch_persist_q(gqmap_ctx *c, int n, bool dry)
 template <typename R, typename VT>
 bool launch_persist_t(gqmap_ctx *c, int n, bool dry)
 {
-    // not Q = 4 (120x160): 57.3 vs 48.8 us/it measured (profiles/r03_persist_levels.txt;
-    // GQ_PERSIST_Q4: experiment builds only)
-#if GQ_PERSIST_Q4
-    if (c->kq == 4) return launch_persist_q<R, VT, 4>(c, n, dry);
-#endif
+    // not Q = 4 (120x160): 57.3 vs 48.8 us/it measured (profiles/r03_persist_levels.txt)
     switch (c->kq) {
     case 8: return launch_persist_q<R, VT, 8>(c, n, dry);
     case 16: return launch_persist_q<R, VT, 16>(c, n, dry);
@@ -3728,9 +3652,8 @@ gqmap_status launch_seq_deferred(gqmap_ctx *c, int n, hipEvent_t *ev = nullptr)
 
 gqmap_status launch_step(gqmap_ctx *c);
 
-// After a run: a deferred sequence, or a dataflow launch deeper than lag 2
-// (GQ_FLOW_LAG), overshot its stop iteration (Ctl::ovr): restore the
-// sequence's / launch's snapshot (state + Ctl at its start) and re-run its
+// After a run: a deferred sequence overshot its stop iteration (Ctl::ovr):
+// restore the sequence's snapshot (state + Ctl at its start) and re-run its
 // first ovr iterations with the exact per-iteration step, which stops at the
 // same iteration as the whole grid.  Every rank sees the same all-gathered
 // totals, so every rank recovers together (the re-run's collectives match).
@@ -3782,9 +3705,6 @@ gqmap_status launch_steps(gqmap_ctx *c, int n)
 void drop_graph(gqmap_ctx *c);
 
 // ---- dataflow launch (k_iter_flow, policy flow) ---------------------------
-#ifndef GQ_FLOW_WIDE_ITEMS  // items per iteration above which the 3-wave form runs
-#define GQ_FLOW_WIDE_ITEMS 4096
-#endif
 template <typename R, typename VT, int ENG, int Q, bool LIT, int W>
 void flow_launch(gqmap_ctx *c, IterParams<R, VT> P, int n, int nitems, int ntiles)
 {
@@ -3896,7 +3816,6 @@ bool launch_flow(gqmap_ctx *c, int n, bool dry)
     if (c->fp32)
         return c->vvp ? !c->lit && c->kq == 1 && launch_flow_q<float, vvh2_t, 0, 1>(c, n, dry)
                       : launch_flow_t<float, float>(c, n, dry);
-#if GQ_TAP_LUT
     // taps by LDS table (the offset store, gqmap_set_images); not the
     // 3-wave form of the large frames, which keeps the pair store's kernel
     // (its edge jobs address the state by 32-bit offsets, GQ_EDGE_ADDR32: a
@@ -3905,7 +3824,6 @@ bool launch_flow(gqmap_ctx *c, int n, bool dry)
     if (c->vvp && c->tapt && c->tiles_m * c->tiles_n <= GQ_FLOW_WIDE_ITEMS &&
         (!GQ_EDGE_ADDR32 || edge_addr32_ok(c->M, c->N, c->L, sizeof(double))))
         return !c->lit && c->kq == 1 && launch_flow_q<double, vvo2_t, 0, 1>(c, n, dry);
-#endif
     if (c->vvp) return !c->lit && c->kq == 1 && launch_flow_q<double, vvh2_t, 0, 1>(c, n, dry);
     if (c->vv32) return launch_flow_t<double, vvs_t>(c, n, dry);
     return launch_flow_t<double, double>(c, n, dry);
@@ -4455,7 +4373,7 @@ gqmap_status gqmap_set_images(gqmap_ctx *c, const double *I1, const double *I2, 
         // the buffer's tail, at most a table's worth.  The pair store stays:
         // the per-launch kernels (the recovery path), gqmap_log_p and the
         // read-back take it.
-        bool tapt = GQ_TAP_LUT && c->pol.tap_lut && !c->fp32;
+        bool tapt = c->pol.tap_lut && !c->fp32;
         int vmin = 0, vmax = 0;
         for (size_t k = 0; tapt && k < VV.size(); ++k) {
             const int vi = (int)VV[k];  // (|v| <= 65504: exact in binary16)
@@ -4793,7 +4711,7 @@ gqmap_status gqmap_run_aepe(gqmap_ctx *c, int n_iter, int *n_done, double *trace
             if ((s = persist_recover(c, &recovered)) != GQMAP_OK) return s;
             if ((s = read_ctl(c, &h)) != GQMAP_OK) return s;
         }
-        if (h.ovr) {  // a deferred RCCL sequence / deep dataflow launch ran past its stop iteration
+        if (h.ovr) {  // a deferred RCCL sequence ran past its stop iteration
             bool again = false;
             if ((s = ovr_recover(c, h, &again)) != GQMAP_OK) return s;
             if ((s = read_ctl(c, &h)) != GQMAP_OK) return s;
@@ -5236,9 +5154,7 @@ int gqmap_debug_flow_per_cu(gqmap_ctx *c)
     DeviceGuard dg(c->device);
     // (above GQ_FLOW_WIDE_ITEMS the 3-wave form of the pair store's kernel, whatever the store)
     if (c->tiles_m * c->tiles_n > GQ_FLOW_WIDE_ITEMS) return kernel_shape(k_iter_flow<double, vvh2_t, 0, 1, false, 3>).x;
-#if GQ_TAP_LUT
     if (c->tapt) return kernel_shape(k_iter_flow<double, vvo2_t, 0, 1, false, 0>).x;
-#endif
     return kernel_shape(k_iter_flow<double, vvh2_t, 0, 1, false, 0>).x;
 }
 

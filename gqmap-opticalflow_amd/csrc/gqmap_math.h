@@ -1354,33 +1354,18 @@ inline void lit_table_point(double *row8, double xi, double xj, double wi, doubl
 // if-chain, each tap weighted as (VV * ss) * tw, the taps added left to right
 // (first column parenthesised as the reference writes it), then /4.
 //
-// Execution forms of the literal loops (GQ_LIT_FORM; every form performs the
-// same IEEE operations on the same operands, so the bits never change --
-// tests/test_literal.py, tests/test_gpu_literal.py):
-//   0  round 5: the reference's if-chain as branches, `if a~=0` per point,
-//      every product of a point formed at the point;
-//   1  the cell chosen branch-free: after the clamp Xq is in [1, N], where
-//      the chain's 1 / floor(Xq) / N-1 is exactly min(floor(Xq), N-1) (the
-//      chain's first arm only sees Xq = 1 = floor(Xq)); `a~=0` is uniform
-//      over a gradient (alpha of one component, one guard flag), so the
-//      loop is versioned on it instead of testing it per point;
-//   2  as 1, and the column's products s*XI, t*XI formed once per meshgrid
-//      column (XI(r, c) = X(c) for every row r, gqmap_gpu_mixture.m:8): the
-//      same rounded products the per-point form computes.
-#ifndef GQ_LIT_FORM
-#define GQ_LIT_FORM 2
-#endif
-// the three changes separately (A/B): branch-free cell, versioned loop,
-// column products (default: those of GQ_LIT_FORM)
-#ifndef GQ_LIT_CELL
-#define GQ_LIT_CELL (GQ_LIT_FORM >= 1)
-#endif
-#ifndef GQ_LIT_HOIST
-#define GQ_LIT_HOIST (GQ_LIT_FORM >= 1)
-#endif
-#ifndef GQ_LIT_CSE
-#define GQ_LIT_CSE (GQ_LIT_FORM >= 2)
-#endif
+// How the literal loops run (the same IEEE operations on the same operands
+// as the reference's statement order, so the same bits -- tests/test_literal.py,
+// tests/test_gpu_literal.py; profiles/r06_lit_form_ab.txt, r06_lit_form_ab2.txt):
+//   - the cell is chosen branch-free: after the clamp Xq is in [1, N], where
+//     the chain's 1 / floor(Xq) / N-1 is exactly min(floor(Xq), N-1) (the
+//     chain's first arm only sees Xq = 1 = floor(Xq));
+//   - `a~=0` is uniform over a gradient (alpha of one component, one guard
+//     flag), so the loop is versioned on it instead of testing it per point;
+//   - the column's products s*XI, t*XI are formed once per meshgrid column
+//     (XI(r, c) = X(c) for every row r, gqmap_gpu_mixture.m:8): the same
+//     rounded products the per-point form computes.
+//
 // fmin / fmax of non-NaN operands (the clamp's): on the device the bare
 // v_min_f64 / v_max_f64.  Through fmin the compiler re-canonicalises the
 // loop-invariant bound (a v_max_f64 x, x) at every quadrature point -- 4 of
@@ -1406,60 +1391,29 @@ GQ_HD double lit_max(double a, double b)
     return fmax(a, b);
 #endif
 }
-#ifndef GQ_LIT_ASM_MINMAX
-#define GQ_LIT_ASM_MINMAX 1
-#endif
-#if GQ_LIT_ASM_MINMAX
-#define GQ_LMIN lit_min
-#define GQ_LMAX lit_max
-#else
-#define GQ_LMIN fmin
-#define GQ_LMAX fmax
-#endif
-// GQ_LIT_ADDR: the four tap columns as one cell offset plus multiples of the
-// column stride (byte offsets, as bicubic_w4) instead of a multiply each.
-// With GQ_LIT_ASM_MINMAX: 174 -> 165 VALU instructions per node-gradient
-// point, k_iter_lit 271.8 -> 268.1 us, graph 255.0 -> 250.4 us per iteration,
-// the same checksum (profiles/r06_lit_minmax_addr_ab.txt).
-#ifndef GQ_LIT_ADDR
-#define GQ_LIT_ADDR 1
-#endif
+// The four tap columns are one cell offset plus multiples of the column
+// stride (byte offsets, as bicubic_w4) instead of a multiply each.  With the
+// bare min / max: 174 -> 165 VALU instructions per node-gradient point,
+// k_iter_lit 271.8 -> 268.1 us, graph 255.0 -> 250.4 us per iteration, the
+// same checksum (profiles/r06_lit_minmax_addr_ab.txt).
 template <typename VP>
 GQ_HD double lit_interp(VP VV, int M2, int Mo, int No, double Xq, double Yq)
 {
-    Xq = GQ_LMIN(GQ_LMAX(Xq, 1.0), (double)No);
-    Yq = GQ_LMIN(GQ_LMAX(Yq, 1.0), (double)Mo);
-#if GQ_LIT_CELL
-    const double fx = GQ_LMIN(floor(Xq), (double)(No - 1)), fy = GQ_LMIN(floor(Yq), (double)(Mo - 1));
+    Xq = lit_min(lit_max(Xq, 1.0), (double)No);
+    Yq = lit_min(lit_max(Yq, 1.0), (double)Mo);
+    const double fx = lit_min(floor(Xq), (double)(No - 1)), fy = lit_min(floor(Yq), (double)(Mo - 1));
     const int ix = (int)fx, iy = (int)fy;
     const double so = Xq - fx, to = Yq - fy;
-#else
-    int ix, iy;
-    if (Xq <= 1.0) ix = 1;
-    else if (Xq <= No - 1) ix = (int)floor(Xq);
-    else ix = No - 1;
-    if (Yq <= 1.0) iy = 1;
-    else if (Yq <= Mo - 1) iy = (int)floor(Yq);
-    else iy = Mo - 1;
-    const double so = Xq - ix, to = Yq - iy;
-#endif
     const double t0 = ((2.0 - to) * to - 1.0) * to;
     const double t1 = (3.0 * to - 5.0) * to * to + 2.0;
     const double t2 = ((4.0 - 3.0 * to) * to + 1.0) * to;
     const double t3 = (to - 1.0) * to * to;
-#if GQ_LIT_ADDR
     constexpr uint32_t E = (uint32_t)sizeof(*VV);
     const uint32_t ob = cell_elem(iy, ix, M2) * E, cb = (uint32_t)M2 * E;
     const auto c1 = byte_ptr(VV, ob);
     const auto c2 = byte_ptr(VV, ob + cb);
     const auto c3 = byte_ptr(VV, ob + 2 * cb);
     const auto c4 = byte_ptr(VV, ob + 3 * cb);
-#else
-    const auto c1 = elem_ptr(VV, cell_elem(iy, ix, M2));
-    const auto c2 = elem_ptr(VV, cell_elem(iy, ix + 1, M2));
-    const auto c3 = elem_ptr(VV, cell_elem(iy, ix + 2, M2));
-    const auto c4 = elem_ptr(VV, cell_elem(iy, ix + 3, M2));
-#endif
     double ss = ((2.0 - so) * so - 1.0) * so;
     double Vq = (((double)c1[0] * ss * t0 + (double)c1[1] * ss * t1) + (double)c1[2] * ss * t2) +
                 (double)c1[3] * ss * t3;
@@ -1472,7 +1426,7 @@ GQ_HD double lit_interp(VP VV, int M2, int Mo, int No, double Xq, double Yq)
     return Vq / 4;
 }
 
-// x / y correctly rounded, given yr = RN(1 / y) (GQ_LIT_MDIV, device only):
+// x / y correctly rounded, given yr = RN(1 / y) (device only):
 // q0 = RN(x yr) is within 1.5 ulp of x / y, one correction
 // RN(q0 + RN(x - y q0) yr) brings it within 1 ulp, and a second is RN(x / y)
 // exactly (Markstein's theorem: yr within half an ulp of 1 / y, q within one
@@ -1481,12 +1435,9 @@ GQ_HD double lit_interp(VP VV, int M2, int Mo, int No, double Xq, double Yq)
 // instead of the 12 of the general IEEE sequence; the host divides.  Round 5
 // (profiles/r05_literal_div_ab.txt): the literal engine's k_iter 327 -> 298 us
 // on C2, still bit-identical to the restatement over 500 iterations.
-#ifndef GQ_LIT_MDIV
-#define GQ_LIT_MDIV 1
-#endif
 GQ_HD double div_rcp(double x, double y, double yr)
 {
-#if GQ_LIT_MDIV && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
     double q = x * yr;
     q = fma(fma(-q, y, x), yr, q);
     return fma(fma(-q, y, x), yr, q);
@@ -1540,23 +1491,11 @@ GQ_HD LitCoef lit_coef(double p)
 }
 
 // Epilogues: node (:107-115, entropy -3T) and edge (:137-145, entropy +T).
-// GQ_LIT_PIDIV: the six divisions by pi as div_rcp with RN(1/pi) (5
-// operations instead of the general division's ~10; the same correctly
-// rounded quotient -- div_rcp's conditions hold: pi's reciprocal rounded
-// once, sums far from overflow and underflow).  Bit-identical over
-// tests/test_gpu_literal.py, but neutral (264.9 vs 263.7 us, 30 of ~32k
-// instructions per node-lane; profiles/r06_lit_xj_pidiv_ab.txt): off.
-#ifndef GQ_LIT_PIDIV
-#define GQ_LIT_PIDIV 0
-#endif
+// The six divisions by pi are plain divisions (as div_rcp with RN(1/pi) they
+// were bit-identical but no faster; profiles/r06_lit_xj_pidiv_ab.txt).
 GQ_HD double lit_div_pi(double x)
 {
-#if GQ_LIT_PIDIV
-    constexpr double rpi = 1.0 / GQ_M_PI;
-    return div_rcp(x, GQ_M_PI, rpi);
-#else
     return x / GQ_M_PI;
-#endif
 }
 GQ_HD Grad<double> lit_epi(const LitAcc &S, const LitCoef &c, double a, double o1, double o2, double p, double T,
                            bool node)
@@ -1585,46 +1524,25 @@ GQ_HD Grad<double> lit_epi(const LitAcc &S, const LitCoef &c, double a, double o
 
 // The quadrature loop of a gradient, points k = r + K c in meshgrid order
 // (column c outer, row r inner: the reference's k = 1..K^2): pt(k, zi, zj)
-// returns the point's fval.  Form 2 forms s*XI and t*XI once per column.
-// GQ_LIT_XJ_PREFETCH: the next point's XJ (a scalar load) issued during
-// this point, so a point does not start with a wait on the scalar cache.
-// Measured 263.7 -> 298.3 us (the node loop's schedule falls apart, as with
-// GQ_LIT_NODE_UNROLL; profiles/r06_lit_xj_pidiv_ab.txt): off.
-#ifndef GQ_LIT_XJ_PREFETCH
-#define GQ_LIT_XJ_PREFETCH 0
-#endif
+// returns the point's fval.  s*XI and t*XI are formed once per column, and
+// each point loads its own XJ (loading it a point early cost the node loop
+// its schedule; profiles/r06_lit_xj_pidiv_ab.txt).
 template <bool LIVE, typename TP, typename PT>
 GQ_HD void lit_points(TP tab, int K2, const LitCoef &c, double p, LitAcc &S, PT pt)
 {
-#if GQ_LIT_CSE
     const int K = lit_k(K2);
-#if GQ_LIT_XJ_PREFETCH
-    double XJn = tab[tab_at(TL_XJ, 0)];
-#endif
     for (int cc = 0, k = 0; cc < K; ++cc) {
         const double XI = tab[tab_at(TL_XI, k)];
         const double sXI = c.s * XI, tXI = c.t * XI;
         for (int r = 0; r < K; ++r, ++k) {
-#if GQ_LIT_XJ_PREFETCH
-            const double XJ = XJn;
-            XJn = tab[tab_at(TL_XJ, k + 1 < K2 ? k + 1 : k)];
-#else
             const double XJ = tab[tab_at(TL_XJ, k)];
-#endif
             const double zi = sXI + c.t * XJ, zj = tXI + c.s * XJ;
             S.add(tab, k, pt(k, zi, zj), zi, zj, p, c.sqrtpr, c.rsqrtpr, LIVE);
         }
     }
-#else
-    for (int k = 0; k < K2; ++k) {
-        const double XI = tab[tab_at(TL_XI, k)], XJ = tab[tab_at(TL_XJ, k)];
-        const double zi = c.s * XI + c.t * XJ, zj = c.t * XI + c.s * XJ;
-        S.add(tab, k, pt(k, zi, zj), zi, zj, p, c.sqrtpr, c.rsqrtpr, LIVE);
-    }
-#endif
 }
 
-// Form 3 (GQ_LIT_MIRROR, edge gradients at K = 9): rows r and K-1-r of a
+// The edge gradients' loop at K = 9: rows r and K-1-r of a
 // meshgrid column share A = XI^2+XJ^2, M = XI^2-XJ^2 and A - 1 exactly (the
 // library's Gauss-Hermite rule is symmetric: x(K-1-i) = -x(i), the middle
 // node 0 -- gauss_hermite), so the same p - p*A, the same division M/sqrtpr
@@ -1632,13 +1550,9 @@ GQ_HD void lit_points(TP tab, int K2, const LitCoef &c, double p, LitAcc &S, PT 
 // reuses the earlier row's rounded values instead of recomputing them: the
 // same operations on the same operands as the per-point form, in the same
 // accumulation order.  The column's pending values live in registers (the
-// column loop fully unrolled).
-#ifndef GQ_LIT_MIRROR
-#define GQ_LIT_MIRROR 1
-#endif
-#ifndef GQ_LIT_MIRROR_NODE  // the same sharing in the node gradient's loop
-#define GQ_LIT_MIRROR_NODE 0
-#endif
+// column loop fully unrolled).  The node gradient keeps the runtime-K loop:
+// this sharing, or its rows unrolled 2 or 3 times, cost it its schedule at
+// the 3-wave bound (profiles/r06_lit_mirror_ab.txt, r06_lit_minmax_addr_ab.txt).
 template <int KK, typename TP, typename PT>
 GQ_HD void lit_points_mirror(TP tab, const LitCoef &c, double p, LitAcc &S, PT pt)
 {
@@ -1677,65 +1591,13 @@ GQ_HD void lit_points_mirror(TP tab, const LitCoef &c, double p, LitAcc &S, PT p
     }
 }
 
-// The node gradient's loop at K = 9 with the rows unrolled GQ_LIT_NODE_UNROLL
-// times (1: the runtime-K loop): the next point's tap gathers can then issue
-// before this point's taps are summed.  The same operations in the same order.
-// Measured 2 / 3: 297.8 / 298.2 against 268.1 us (register pressure at the
-// 3-wave bound; profiles/r06_lit_minmax_addr_ab.txt): not used.
-#ifndef GQ_LIT_NODE_UNROLL
-#define GQ_LIT_NODE_UNROLL 1
-#endif
-template <int KK, typename TP, typename PT>
-GQ_HD void lit_points_fixed(TP tab, const LitCoef &c, double p, LitAcc &S, PT pt)
-{
-    for (int cc = 0, k0 = 0; cc < KK; ++cc, k0 += KK) {
-        const double XI = tab[tab_at(TL_XI, k0)];
-        const double sXI = c.s * XI, tXI = c.t * XI;
-#ifdef __HIPCC__
-#pragma unroll GQ_LIT_NODE_UNROLL
-#endif
-        for (int r = 0; r < KK; ++r) {
-            const int k = k0 + r;
-            const double XJ = tab[tab_at(TL_XJ, k)];
-            const double zi = sXI + c.t * XJ, zj = tXI + c.s * XJ;
-            S.add(tab, k, pt(k, zi, zj), zi, zj, p, c.sqrtpr, c.rsqrtpr, true);
-        }
-    }
-}
-
-template <typename TP, typename PT>
-GQ_HD void lit_points_dyn(TP tab, int K2, const LitCoef &c, double p, LitAcc &S, PT pt, bool live)
-{
-#if GQ_LIT_CSE
-    const int K = lit_k(K2);
-    for (int cc = 0, k = 0; cc < K; ++cc) {
-        const double XI = tab[tab_at(TL_XI, k)];
-        const double sXI = c.s * XI, tXI = c.t * XI;
-        for (int r = 0; r < K; ++r, ++k) {
-            const double XJ = tab[tab_at(TL_XJ, k)];
-            const double zi = sXI + c.t * XJ, zj = tXI + c.s * XJ;
-            S.add(tab, k, pt(k, zi, zj), zi, zj, p, c.sqrtpr, c.rsqrtpr, live);
-        }
-    }
-#else
-    for (int k = 0; k < K2; ++k) {
-        const double XI = tab[tab_at(TL_XI, k)], XJ = tab[tab_at(TL_XJ, k)];
-        const double zi = c.s * XI + c.t * XJ, zj = c.t * XI + c.s * XJ;
-        S.add(tab, k, pt(k, zi, zj), zi, zj, p, c.sqrtpr, c.rsqrtpr, live);
-    }
-#endif
-}
-
+// The loop versioned on `live` (uniform over a gradient) instead of testing
+// it at every point
 template <typename TP, typename PT>
 GQ_HD void lit_loop(TP tab, int K2, const LitCoef &c, double p, bool live, LitAcc &S, PT pt)
 {
-#if GQ_LIT_HOIST
     if (live) lit_points<true>(tab, K2, c, p, S, pt);
     else lit_points<false>(tab, K2, c, p, S, pt);
-#else
-    // `live` tested at every point (LitAcc::add)
-    lit_points_dyn(tab, K2, c, p, S, pt, live);
-#endif
 }
 
 // node_grad_spectral with node_pot, (m, n) 0-based pixel of the frame
@@ -1754,14 +1616,7 @@ GQ_HD Grad<double> lit_node_grad(TP tab, int K2, VP VV, int M2, IP I1, int Mo, i
         const double d = I - lit_interp(VV, M2, Mo, No, (double)(n + 1) + x1, (double)(m + 1) + x2);
         return tab[tab_at(TL_W, k)] * (-lamd * GQ_SQRT(eps + d * d));
     };
-#if GQ_LIT_MIRROR && GQ_LIT_MIRROR_NODE
-    if (K2 == 81 && live) lit_points_mirror<9>(tab, c, p, S, pt);
-    else
-#elif GQ_LIT_NODE_UNROLL > 1
-    if (K2 == 81 && live) lit_points_fixed<9>(tab, c, p, S, pt);
-    else
-#endif
-        lit_loop(tab, K2, c, p, live, S, pt);
+    lit_loop(tab, K2, c, p, live, S, pt);
     return lit_epi(S, c, a, o1, o2, p, T, true);
 }
 
@@ -1778,11 +1633,8 @@ GQ_HD Grad<double> lit_edge_grad(TP tab, int K2, double eps, double lams, bool g
         const double d = (so1 * zi + u1) - (so2 * zj + u2);
         return tab[tab_at(TL_W, k)] * (-lams * GQ_SQRT(eps + d * d));
     };
-#if GQ_LIT_MIRROR
     if (K2 == 81 && live) lit_points_mirror<9>(tab, c, p, S, pt);
-    else
-#endif
-        lit_loop(tab, K2, c, p, live, S, pt);
+    else lit_loop(tab, K2, c, p, live, S, pt);
     return lit_epi(S, c, a, o1, o2, p, T, false);
 }
 

@@ -1,9 +1,14 @@
 // gqmap_tuning.h -- compile-time knobs of the HIP iteration kernels
-// (gqmap_engine.hip).  None of them changes a result: every setting computes
-// the same bits (the arithmetic is specified by gqmap_math.h); they choose
-// unrolling, register budgets and kernel shapes.  The defaults are the
-// measured best on MI355X (profiles/ named per knob).  A -D on
-// the compiler line overrides one for an A/B build (scripts/ab_build.sh).
+// (gqmap_engine.hip), all of them.  What is left here is a number that a new
+// device or compiler may move (unroll factors, register budgets, sleeps, a
+// launch's length), a form whose other arm is some other kernel's live code
+// (the halo chain, the trimmed item, the rotated node loop), or diagnostic
+// instrumentation.  None of them changes a result (the arithmetic is
+// specified by gqmap_math.h).  The defaults are the measured best on MI355X
+// (profiles/ named per knob); a -D on the compiler line
+// overrides one for an A/B build (scripts/ab_build.sh).  A switch whose
+// experiment is closed is retired: the winner becomes the code and
+// DESIGN.md 8 records the loser.
 #pragma once
 
 // Edge quadrature: mirror pairs per loop trip, fp64 and fp32 (r02_pair_unroll)
@@ -23,56 +28,8 @@
 #ifndef GQ_NODE_UNROLL_N
 #define GQ_NODE_UNROLL_N 1
 #endif
-// Finalize: the NFIX fixed sums loaded together (fp32 C2 -2 us)
-#ifndef GQ_FIN_GROUP
-#define GQ_FIN_GROUP 1
-#endif
-// fp32: mirror-pair edge sums on packed float2 registers (r02_lane_mask_pk)
-#ifndef GQ_EDGE_PK
-#define GQ_EDGE_PK 1
-#endif
-// Q > 1: the quadrature table staged in LDS (lane-varying indices)
-#ifndef GQ_TAB_LDS
-#define GQ_TAB_LDS 1
-#endif
-// Co-resident workgroups alternate node-first / edge-first phase order
-#ifndef GQ_PHASE_MIX
-#define GQ_PHASE_MIX 1
-#endif
-// ... with the order flipped (co-resident blocks j, j+S, j+2S: edge, node,
-// edge) on the ctf Q = 1 kernel (profiles/r05_phase_mix_inv.txt)
-#ifndef GQ_PHASE_MIX_CTF_Q1_INV
-#define GQ_PHASE_MIX_CTF_Q1_INV 1
-#endif
-#ifndef GQ_PHASE_MIX_OTHER_INV  // the other single-pixel kernels
-#define GQ_PHASE_MIX_OTHER_INV 0
-#endif
-// Waves per SIMD the register allocation must allow (MI355X: 136-168 VGPRs
-// -> 3, 176-256 -> 2).  Left to the allocator: forcing 3 waves on the
-// single-scale engine moved arrays to scratch (C2 +24%); bounding the super
-// engine to 2 made its block sum 25% slower than the allocator's own schedule.
-#ifndef GQ_MIN_WAVES
-#define GQ_MIN_WAVES 1
-#endif
-#ifndef GQ_SUPER_WAVES
-#define GQ_SUPER_WAVES 1
-#endif
-#ifndef GQ_MIDQ_WAVES  // single-pixel engines at Q = 2, 4, 8
-#define GQ_MIDQ_WAVES 1
-#endif
-// Smallest lanes-per-node split whose edge jobs prefetch the next job's
-// operands / run fully unrolled (r02_edge_prefetch_ab)
-#ifndef GQ_PREFETCH_MIN_Q
-#define GQ_PREFETCH_MIN_Q 2
-#endif
-// Node quadrature software-pipelined (node_sums PF) from this many lanes per
-// node up; 99 = never.  Round 5 (profiles/r05_node_pf_ab.txt): C2 fp64
-// k_iter -1.3%, ctf 480x640 -0.5%, 388x75 strip -1%, 240x320 / 120x160
-// unchanged, same bits; the C2 kernel at 164 VGPRs instead of 168.
-#ifndef GQ_NODE_PF_MIN_Q
-#define GQ_NODE_PF_MIN_Q 1
-#endif
-// Form of that loop per instantiation (node_sums ROT).  Trips per loop pass
+// Form of the software-pipelined node loop per instantiation (node_sums PF,
+// ROT).  Trips per loop pass
 // of the fp64 mixture item of the dataflow launch at one lane per node on the
 // binary16 pair store (C2's kernel): 4 (profiles/node_rotate_ab.txt: C2 fp64 -1.3%; 2: -0.9%, 3: -1.2%,
 // 9: -0.6%).  The loop rotated by one stage (a sum of NODE_ROT 1 and
@@ -94,22 +51,16 @@
 //   0  wave 0 runs it as a fifth job after its four own
 //   1  the chain: each of the four waves runs a quarter of its pair range for
 //      all 64 edges and hands the sums on through LDS, same order of the sums
-//   2  rotation: as 0, on wave GQ_FLOW_HALO_ROT_WAVE in the edge-first
-//      workgroup of a CU's two (wave 0 in the node-first one)
 // GQ_FLOW_HALO: the fp64 mixture item on the binary16 pair store (C2's
-// kernel) -- 1: C2 fp64 -1.6 / -1.7% in two sessions, every round ahead; 2:
-// +0.2% (the co-resident workgroups' halo waves already sit on different
-// SIMDs); profiles/halo_chain_ab.txt, halo_chain_placement.txt, DESIGN.md 4.
+// kernel) -- 1: C2 fp64 -1.6 / -1.7% in two sessions, every round ahead;
+// profiles/halo_chain_ab.txt, halo_chain_placement.txt, DESIGN.md 4.
 // GQ_FLOW_HALO_CTF: the fp64 coarse-to-fine levels at one lane per node -- 1:
-// C3 -1.0 / -1.1% (same file; 2 not measured there).
+// C3 -1.0 / -1.1% (same file).
 #ifndef GQ_FLOW_HALO
 #define GQ_FLOW_HALO 1
 #endif
 #ifndef GQ_FLOW_HALO_CTF
 #define GQ_FLOW_HALO_CTF 1
-#endif
-#ifndef GQ_FLOW_HALO_ROT_WAVE
-#define GQ_FLOW_HALO_ROT_WAVE 2
 #endif
 // the chain: the centre point and the epilogue, which the last wave runs
 // after its slice, counted in mirror pairs -- its slice is that much shorter
@@ -120,18 +71,9 @@
 #ifndef GQ_FLOW_HALO_SLEEP  // the chain: s_sleep between two polls of the hand-over flag
 #define GQ_FLOW_HALO_SLEEP 1
 #endif
-// Tap conversion by LDS table in the fp64 mixture item of the dataflow launch
-// at one lane per node (k_iter_flow<double, vvo2_t, 0, 1>, plain and grouped
-// items; not the 3-wave large-frame form): integer frames within a table's
-// range (gqmap_math.h TAPLUT_N) get an offset store beside the binary16 pair
-// store, and a tap is a 16-bit extraction and a ds_read_b64 in place of two
-// conversions.  0: the kernel is not built and every frame takes the pair
-// store's kernel (run-time: policy tap_lut).
-#ifndef GQ_TAP_LUT
-#define GQ_TAP_LUT 1
-#endif
 // Address arithmetic, copies and cross-lane traffic around the quadrature
-// loops of that item (iter_tile TRIM; the floating-point instructions are
+// loops of the fp64 mixture item on the offset store (k_iter_flow<double,
+// vvo2_t, 0, 1>; iter_tile TRIM; the floating-point instructions are
 // gqmap_math.h's and stay; every other instantiation keeps its code).
 // profiles/item_trim_ab.txt: the first two together C2 fp64 -0.9 / -0.6% in
 // two sessions (each alone +0.2 / +0.3%: inside the spread), all three
@@ -156,19 +98,40 @@
 #ifndef GQ_FIXSUM_DPP
 #define GQ_FIXSUM_DPP 1
 #endif
-#ifndef GQ_UNROLL_MIN_Q
-#define GQ_UNROLL_MIN_Q 2
-#endif
-// Persistent small-level launch: also at Q = 4 (r03_persist_levels: slower, off)
-#ifndef GQ_PERSIST_Q4
-#define GQ_PERSIST_Q4 0
-#endif
-// Persistent grid barrier: s_sleep between polls
+// Persistent grid barrier and the dataflow launch's waits: s_sleep between polls
 #ifndef GQ_PERSIST_SLEEP
 #define GQ_PERSIST_SLEEP 2
+#endif
+// Waves per SIMD the register allocation must allow (__launch_bounds__; 1:
+// the allocator's choice, which every per-launch fast kernel keeps).  The
+// literal kernel (k_iter_lit); the dataflow kernel at one lane per node and
+// its literal-order instantiation (k_iter_flow; profiles/r06_flow_2waves_ab.txt,
+// r06_lit_flow_2waves_ab.txt)
+#ifndef GQ_LIT_WAVES
+#define GQ_LIT_WAVES 3
+#endif
+#ifndef GQ_FLOW_WAVES
+#define GQ_FLOW_WAVES 2
+#endif
+#ifndef GQ_FLOW_LIT_WAVES
+#define GQ_FLOW_LIT_WAVES 2
+#endif
+// Iterations per launch of a dataflow context (FLOW_CHUNK;
+// profiles/flow_groups_chunk_ab.txt, flow_launch_fixed_cost.txt)
+#ifndef GQ_FLOW_CHUNK
+#define GQ_FLOW_CHUNK 250
+#endif
+// Items per iteration above which the dataflow launch runs its 3-wave form
+#ifndef GQ_FLOW_WIDE_ITEMS
+#define GQ_FLOW_WIDE_ITEMS 4096
 #endif
 // Debug builds only: per-workgroup s_memrealtime stamps of k_iter iterations
 // GQ_TIMELINE and GQ_TIMELINE + 1 (gqmap_debug_timeline, scripts/timeline.py)
 #ifndef GQ_TIMELINE
 #define GQ_TIMELINE 0
+#endif
+// Diagnostic builds only: the dataflow launch's timeline, per item and per
+// wave (k_iter_flow; scripts/flow_timeline.py, halo_placement.py)
+#ifndef GQ_FLOW_TL
+#define GQ_FLOW_TL 0
 #endif

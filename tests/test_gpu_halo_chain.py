@@ -85,7 +85,7 @@ def _same(a, b):
 
 def test_crops_have_the_tiles_they_are_for():
     assert (-(-48 // 16), -(-40 // 16), 40 % 16) == (3, 3, 8)
-    assert 36 - 2 * 16 == 4  # at most 4 node rows: the last tile row is grouped (GQ_FLOW_GROUPS)
+    assert 36 - 2 * 16 == 4  # at most 4 node rows: the last tile row is grouped (k_iter_flow GRP)
 
 
 @pytest.mark.parametrize("K", KS)

@@ -127,7 +127,7 @@ def _vs_cpu_model(rows, cols, K, kind, got):
 
 def test_crops_have_the_tiles_they_are_for():
     assert (-(-40 // 16), -(-56 // 16), 40 % 16, 56 % 16) == (3, 4, 8, 8)
-    assert 36 - 2 * 16 == 4  # at most 4 node rows: the last tile row is grouped (GQ_FLOW_GROUPS)
+    assert 36 - 2 * 16 == 4  # at most 4 node rows: the last tile row is grouped (k_iter_flow GRP)
 
 
 def test_which_contexts_take_the_offset_store():
