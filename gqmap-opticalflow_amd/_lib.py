@@ -46,6 +46,7 @@ EXPORTS = (
     "gqmap_block_match_window_multi", "gqmap_block_match_window_multi_host", "gqmap_block_match_pyramid_multi",
     "gqmap_block_match_pyramid_multi_host",
     "gqmap_flow_denoise", "gqmap_flow_denoise_device", "gqmap_flow_denoise_host",
+    "gqmap_flow_wmedian", "gqmap_flow_wmedian_host",
 )
 CTF_MAX_LEVELS = 8
 
@@ -197,6 +198,10 @@ def load():
         "gqmap_flow_consistency_host": (C.c_int, [_D, _D, C.c_int, C.c_int, C.c_double, C.c_double, _D, u8]),
         "gqmap_flow_fill": (C.c_int, [_D, u8, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _D, u8, _D, C.c_int]),
         "gqmap_flow_fill_host": (C.c_int, [_D, u8, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _D, u8]),
+        "gqmap_flow_wmedian": (C.c_int, [_D, _D, _D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _D, _D,
+                                         C.c_int]),
+        "gqmap_flow_wmedian_host": (C.c_int, [_D, _D, _D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                              _D]),
         "gqmap_structure_texture": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _D, _D,
                                               _D, C.c_int]),
         "gqmap_structure_texture_host": (C.c_int, [_D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,

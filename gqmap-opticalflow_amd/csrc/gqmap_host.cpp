@@ -15,6 +15,7 @@
 #include "gqmap_flowcheck.h"
 #include "gqmap_internal.h"
 #include "gqmap_rof.h"
+#include "gqmap_wmedian.h"
 
 namespace gq {
 
@@ -912,6 +913,81 @@ gqmap_status gqmap_flow_denoise_host(const gqmap_cpu_options *o, const double *f
     const int done = o->K == 9 ? dn_host_run<9>(o, R, flow, var, M, N, adjoint, mu, sigma, rou, trace)
                                : dn_host_run<0>(o, R, flow, var, M, N, adjoint, mu, sigma, rou, trace);
     if (its_done) *its_done = done;
+    return GQMAP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Weighted median filter, host model: the arithmetic of gqmap_wmedian.h, pixel
+// by pixel.  The window's live entries are sorted by key and the integer
+// weights summed from the smallest key up; the columns are split among the
+// threads, and a pixel's result depends on the pass's input alone, so the
+// thread count shows in no result.  Bit for bit what gqmap_flow_wmedian
+// computes.
+// ---------------------------------------------------------------------------
+extern "C" {
+
+gqmap_status gqmap_flow_wmedian_host(const double *flow, const double *guide, const double *conf, int M, int N, int r,
+                                     double sigma_s, double sigma_c, int passes, double *out)
+{
+    gq::clear_error();
+    GQ_CHECK(flow && guide && out, GQMAP_ERR_INVALID_ARG, "gqmap_flow_wmedian_host: null argument");
+    const char *bad = gq::wm_bad(M, N, r, sigma_s, sigma_c, passes);
+    GQ_CHECK(!bad, GQMAP_ERR_INVALID_ARG,
+             "gqmap_flow_wmedian_host: %s (M=%d N=%d r=%d sigma_s=%g sigma_c=%g passes=%d)", bad, M, N, r, sigma_s,
+             sigma_c, passes);
+    const gq::WmFilter f = gq::wm_filter(r, sigma_s);
+    const size_t MN = (size_t)M * N;
+    std::vector<uint64_t> cur(2 * MN), nxt(2 * MN);
+    std::memcpy(cur.data(), flow, sizeof(double) * 2 * MN);
+    for (int p = 1; p <= passes; ++p) {
+        dn_columns(dn_threads(), N, [&](int, int n0, int n1) {
+            std::vector<uint32_t> wq;
+            std::vector<std::pair<uint64_t, uint32_t>> live;
+            for (int n = n0; n < n1; ++n)
+                for (int m = 0; m < M; ++m) {
+                    const int i0 = std::max(m - r, 0), i1 = std::min(m + r, M - 1);
+                    const int j0 = std::max(n - r, 0), j1 = std::min(n + r, N - 1);
+                    const size_t o = m + (size_t)M * n;
+                    wq.clear();
+                    for (int j = j0; j <= j1; ++j)
+                        for (int i = i0; i <= i1; ++i) {
+                            const size_t q = i + (size_t)M * j;
+                            wq.push_back(gq::wm_wq(f.s[i - m + r] * f.s[j - n + r], guide[q], guide[o], sigma_c,
+                                                   conf ? conf[q] : 1.0));
+                        }
+                    for (int c = 0; c < 2; ++c) {
+                        const uint64_t *plane = &cur[c * MN];
+                        live.clear();
+                        uint32_t total = 0, e = 0;
+                        for (int j = j0; j <= j1; ++j)
+                            for (int i = i0; i <= i1; ++i, ++e) {
+                                const uint64_t key = gq::wm_key(plane[i + (size_t)M * j]);
+                                if (wq[e] > 0 && !gq::wm_key_nan(key)) {
+                                    live.emplace_back(key, wq[e]);
+                                    total += wq[e];
+                                }
+                            }
+                        uint64_t bits = plane[o];
+                        if (total > 0) {
+                            std::sort(live.begin(), live.end());
+                            uint32_t cum = 0;
+                            for (const auto &kv : live) {
+                                cum += kv.second;
+                                if (2 * cum >= total) {
+                                    bits = gq::wm_unkey(kv.first);
+                                    break;
+                                }
+                            }
+                        }
+                        nxt[c * MN + o] = bits;
+                    }
+                }
+        });
+        cur.swap(nxt);
+    }
+    std::memcpy(out, cur.data(), sizeof(double) * 2 * MN);
     return GQMAP_OK;
 }
 

@@ -613,7 +613,7 @@ def block_match_init(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
 
 def block_match_flow(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float = 1.7, levels: int = 1, pyr_r: int = 1,
                      pyr_k: int = 1, var_scale: float = 1.0, var_default: float = 1.0, weighted: bool = True,
-                     denoise: dict | None = None, device: int = 0, host: bool = False):
+                     denoise: dict | None = None, device: int = 0, host: bool = False, median: dict | None = None):
     """A flow from two frames alone: the block-matching start, checked both
     ways and refilled, then denoised.  block_match_init(subpixel=True,
     sigma_from_cost=True, consistency=True, fill=True) with U, V, ft, sigma,
@@ -630,8 +630,12 @@ def block_match_flow(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
     are Laplace estimates under the engine's data term, not calibrated errors.
     Returns (flow, sigma, consistent): the denoised mean and its width
     (M x N x 2) and the forward-backward verdict (M x N bool).  host=True runs
-    every stage on the library's host models (no device; bit-identical)."""
-    from .ops import flow_denoise
+    every stage on the library's host models (no device; bit-identical).
+    median: a dict of ops.flow_wmedian's keywords (r, sigma_s, sigma_c, passes,
+    conf); the denoised mean then goes through flow_wmedian with I1 as guide
+    before it is returned.  conf="sigma" stands for flow_confidence of the
+    returned width.  median=None (the default) filters nothing."""
+    from .ops import flow_denoise, flow_wmedian
     start, _, sig, cons = block_match_init(I1, I2, U, V, ft, sigma, device=device, host=host, subpixel=True,
                                            sigma_from_cost=True, consistency=True, fill=True, levels=levels,
                                            pyr_r=pyr_r, pyr_k=pyr_k)
@@ -645,7 +649,30 @@ def block_match_flow(I1, I2, U: int = 7, V: int = 7, ft: int = 3, sigma: float =
         var = np.full(start.shape, float(var_default))
     mu0 = np.where(np.isnan(start), 0.0, start)
     mu, sg, _ = flow_denoise(obs, var, mu0, options=kw, device=device, host=host, **call)
+    if median is not None:
+        mkw = dict(median)
+        if isinstance(mkw.get("conf"), str):
+            if mkw["conf"] != "sigma":
+                raise ValueError(f"block_match_flow: median conf must be an array or 'sigma', got {mkw['conf']!r}")
+            mkw["conf"] = flow_confidence(sg)
+        mu = flow_wmedian(mu, I1, device=device, host=host, **mkw)
     return mu, sg, cons
+
+
+def flow_confidence(sigma, s0: float = 1.0):
+    """A confidence map for ops.flow_wmedian from a width per pixel and axis:
+    1 / (1 + (su^2 + sv^2) / s0^2) of an M x N x 2 sigma, as block_match_flow,
+    block_match_init(sigma_from_cost=True) and the engines return it.  A host
+    numpy array in (0, 1]; NaN in gives NaN out, which flow_wmedian takes as
+    weight 0.  s0, the width at which (with su = sv = s0 / sqrt(2)) the
+    confidence is one half, is a knob nobody has tuned."""
+    sigma = np.asarray(sigma, dtype=np.float64)
+    if sigma.ndim != 3 or sigma.shape[2] != 2:
+        raise ValueError("flow_confidence: sigma must be M x N x 2")
+    if not (s0 > 0 and np.isfinite(s0)):
+        raise ValueError("flow_confidence: s0 must be finite and > 0")
+    su, sv = sigma[:, :, 0], sigma[:, :, 1]
+    return np.asfortranarray(1.0 / (1.0 + (su * su + sv * sv) / (float(s0) * float(s0))))
 
 
 def _mean_of_known(x, axis):

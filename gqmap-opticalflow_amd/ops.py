@@ -13,6 +13,7 @@ structure_texture  ROF structure-texture frames (optical_flowSuper.m:7-14, prepr
 flow_consistency   forward-backward check of two flows (csrc/gqmap_flowcheck.h)
 flow_fill          rejected pixels refilled from the valid ones around them
 flow_denoise       weighted flow denoising: per-pixel variance, missing data, adjoint scatter (csrc/gqmap_denoise.h)
+flow_wmedian       weighted median filter guided by an image and a confidence map (csrc/gqmap_wmedian.h)
 """
 from __future__ import annotations
 
@@ -303,6 +304,42 @@ def flow_fill(flow, mask, r: int = 8, sigma: float = 4.0, passes: int = 2, devic
     check(getattr(lib, name)(dptr(flow), u8ptr(mask), M, N, int(r), float(sigma), int(passes), dptr(out), u8ptr(filled),
                              *tail), name)
     return (out, filled, ms.value) if timed else (out, filled)
+
+
+def flow_wmedian(flow, guide, r: int = 2, sigma_s: float = 2.0, sigma_c: float = 10.0, passes: int = 1, conf=None,
+                 device: int = 0, host: bool = False, timed: bool = False):
+    """Weighted median filter of a flow (gqmap_flow_wmedian; csrc/gqmap_wmedian.h
+    holds the specification): per plane the lower weighted median over the
+    (2r+1)^2 window, the entry (i, j) of pixel (m, n) weighing
+    exp(-((i-m)^2 + (j-n)^2) / 2 sigma_s^2) / (1 + ((guide(i,j) - guide(m,n)) / sigma_c)^2)
+    [* conf(i,j)], taken to 16 fractional bits; `passes` Jacobi passes with
+    guide and conf fixed.  flow: M x N x 2, guide: M x N, conf: M x N or None (1
+    everywhere).  Returns the filtered flow; every value of it is one of its
+    window's own bit patterns.  NaN entries and entries without a weight (below
+    2^-16, NaN guide or conf) take no part; a pixel with nothing to choose from
+    keeps its bits.  So r = 0 is the identity, a NaN pixel is filled from what is
+    in reach, and a pixel with conf = 0 never contributes, even after it has been
+    replaced: to inpaint, mark pixels NaN instead.  host=True runs the library's
+    host model (no device; bit-identical).  timed=True returns (flow, kernel
+    time in ms)."""
+    flow = f64(flow)
+    if flow.ndim != 3 or flow.shape[2] != 2:
+        raise ValueError("flow_wmedian: flow must be M x N x 2")
+    M, N, _ = flow.shape
+    if np.shape(guide) != (M, N):
+        raise ValueError(f"flow_wmedian: guide must be {M}x{N}, got {np.shape(guide)}")
+    if conf is not None and np.shape(conf) != (M, N):
+        raise ValueError(f"flow_wmedian: conf must be {M}x{N}, got {np.shape(conf)}")
+    guide = f64(guide)
+    conf = None if conf is None else f64(conf)
+    out = np.zeros((M, N, 2), order="F")
+    lib = _lib.load()
+    ms = C.c_double(float("nan"))
+    tail = () if host else (C.cast(C.byref(ms), _lib._D) if timed else None, device)
+    name = "gqmap_flow_wmedian" + ("_host" if host else "")
+    check(getattr(lib, name)(dptr(flow), dptr(guide), None if conf is None else dptr(conf), M, N, int(r),
+                             float(sigma_s), float(sigma_c), int(passes), dptr(out), *tail), name)
+    return (out, ms.value) if timed else out
 
 
 def structure_texture(im, theta: float = 0.125, n_iter: int = 100, alp: float = 0.95, device: int = 0,

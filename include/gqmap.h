@@ -462,6 +462,30 @@ gqmap_status gqmap_flow_fill(const double *flow, const unsigned char *mask, int 
 gqmap_status gqmap_flow_fill_host(const double *flow, const unsigned char *mask, int M, int N, int r,
                                   double sigma, int passes, double *out, unsigned char *filled);
 
+/* Weighted median filter of a flow over a (2r+1)^2 window, guided by an image
+ * and an optional confidence map (fp64, operation order and the full
+ * specification: csrc/gqmap_wmedian.h).  The entry (i, j) of the window of
+ * pixel (m, n) weighs
+ *   w = (s[i-m+r] s[j-n+r]) (1 / (1 + d^2)) [C(i,j)],  d = (G(i,j) - G(m,n)) / sigma_c,
+ *   s[k] = exp(-(k-r)^2 / 2 / sigma_s^2),
+ * taken to 16 fractional bits (below 2^-16, or NaN: 0).  Per plane the output
+ * is the lower weighted median of the entries with a weight that are not NaN:
+ * the smallest value v with 2 sum_{value <= v} w >= sum w, one of the window's
+ * own bit patterns; with nothing to choose from the pixel keeps its bits.  So
+ * r = 0 is the identity, a NaN pixel is filled from what is in reach, and a
+ * pixel of confidence 0 never contributes.  `passes` Jacobi passes; guide and
+ * conf stay fixed.
+ * flow, out: M x N x 2; guide: M x N; conf: M x N or NULL (1 everywhere).
+ * M, N >= 1, r in [0, 8], sigma_s and sigma_c finite and > 0, passes in [1, 8].
+ * elapsed_ms (may be NULL): kernel time by HIP events, copies excluded. */
+gqmap_status gqmap_flow_wmedian(const double *flow, const double *guide, const double *conf, int M,
+                                int N, int r, double sigma_s, double sigma_c, int passes,
+                                double *out, double *elapsed_ms, int device);
+/* the same on the host, bit for bit */
+gqmap_status gqmap_flow_wmedian_host(const double *flow, const double *guide, const double *conf,
+                                     int M, int N, int r, double sigma_s, double sigma_c,
+                                     int passes, double *out);
+
 /* Structure-texture preprocessing: the generator of the frames
  * optical_flowSuper.m:7-14 loads with preprocessed = true (ROF decomposition by
  * Chambolle's dual projection; reference values theta = 1/8, n_iter = 100,
