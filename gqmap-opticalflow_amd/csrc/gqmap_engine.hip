@@ -1052,7 +1052,10 @@ __device__ __forceinline__ auto tile_frame_view(const IterParams<R, VT> &P, cons
 // C2's kernel -- gqmap_tuning.h GQ_TAP_BIAS, GQ_EDGE_ADDR32): integer and
 // copy instructions around the quadrature loops taken out, the arithmetic of
 // gqmap_math.h on the same operands.
-constexpr int TRIM_TAP_BIAS = 1, TRIM_EDGE_ADDR32 = 2, TRIM_FIXSUM_DPP = 4;
+// TRIM_EDGE_SCHED (GQ_EDGE_SCHED): the edge pair loop is
+// edge_sums_range_sched, the table rows and the two roots of a pair scheduled
+// by hand; the same sums.
+constexpr int TRIM_TAP_BIAS = 1, TRIM_EDGE_ADDR32 = 2, TRIM_FIXSUM_DPP = 4, TRIM_EDGE_SCHED = 8;
 template <typename R, typename VT, int ENG, int Q, bool EDGE_FIRST, bool COH = false, bool NT = false,
           bool LIT = false, bool GRP = false, int ROTF = GQ_NODE_ROT_OTHER, int HALO = 0, int TRIM = 0>
 __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, int it, int parity,
@@ -1283,6 +1286,9 @@ __device__ __forceinline__ void iter_tile(const IterParams<R, VT> P, int tile, i
                         const int np = K2 >> 1;
                         const int ka = slice ? chain_cut(np, cw, GQ_FLOW_HALO_EPI) : 0;
                         const int kb = slice ? chain_cut(np, cw + 1, GQ_FLOW_HALO_EPI) : np;
+                        if constexpr ((TRIM & TRIM_EDGE_SCHED) != 0)
+                            edge_sums_range_sched<GQ_EDGE_SCHED>(tab, ka, kb, K2, last, P.epsn, c, hs);
+                        else
                         edge_sums_range<PU>(tab, ka, kb, K2, last, P.epsn, c, hs);
                         if (last) g = edge_epi(hs, c, P.lams, P.guard != 0, T, a, jb.o1, jb.o2, jb.p, ENG == 2);
                     } else {
@@ -2156,7 +2162,7 @@ void k_iter_flow(IterParams<R, VT> P, int n_iter, unsigned *fl, int ntiles, cons
     // the trimmed item (iter_tile TRIM): the same item on the offset store
     constexpr int TRIM = ENG == 0 && Q == 1 && !LIT && W == 0 && sizeof(R) == 8 && GRP && is_vvo2<VT>::value
                              ? (GQ_TAP_BIAS ? TRIM_TAP_BIAS : 0) | (GQ_EDGE_ADDR32 ? TRIM_EDGE_ADDR32 : 0) |
-                                   (GQ_FIXSUM_DPP ? TRIM_FIXSUM_DPP : 0)
+                                   (GQ_FIXSUM_DPP ? TRIM_FIXSUM_DPP : 0) | (GQ_EDGE_SCHED ? TRIM_EDGE_SCHED : 0)
                              : 0;
     HaloChain<R> *hc = nullptr;
     if constexpr (HALO == 1) {

@@ -1094,6 +1094,106 @@ constexpr int node_rot_unroll(int rot) { return (rot >> 8) > 1 ? (rot >> 8) : 1;
 #ifndef GQ_PIN_UNIFORM64  // (a uniform double)
 #define GQ_PIN_UNIFORM64(x) (void)(x)
 #endif
+// edge_sums_range with the trip scheduled by hand (the trimmed dataflow item,
+// iter_tile TRIM_EDGE_SCHED; gqmap_tuning.h GQ_EDGE_SCHED): the same operations
+// on the same operands in the same order per accumulator, so the same bits.
+// kb <= K^2/2 (a range of mirror pairs), and `centre` only with kb = K^2/2.
+// SCHED is a sum of
+//   1  the rows: a pair's XI / XJ are read a pair ahead -- row k + 1 beside
+//      the six weights of row k at the top of pair k, the first pair's in
+//      front of the loop.  k < kb <= np = K^2/2 <= K^2 - 1, so row k + 1 is
+//      min(k + 1, np), a table row for every K >= 2, an empty range and a
+//      one-pair range included, and the centre's row (K odd) after the last
+//      pair: the centre point takes it from there.  The position arithmetic
+//      and both roots stand between the request and add_pair's six FMAs, the
+//      first to wait for it.
+//   2  the roots: fp and fm in two RootStaged, stage by stage side by side,
+//      so each root's dependent chain has the other's to issue beside.
+// Two pairs per loop pass are written out (a loop holding the scheduling
+// barrier is not unrolled by pragma), the odd pair behind it.
+template <int SCHED, typename R, typename TP>
+GQ_HD void edge_sums_range_sched(TP tab, int ka, int kb, int K2, bool centre, R eps, const EdgeCoef<R> &c, Sums<R> &S)
+{
+    constexpr bool ROWS = (SCHED & 1) != 0, ROOTS = (SCHED & 2) != 0;
+    R xi = 0, xj = 0;
+    if constexpr (ROWS) {
+        xi = tab[tab_at(T_XI, ka)];
+        xj = tab[tab_at(T_XJ, ka)];
+        // (awaited here, once per range: a read still pending at the loop's
+        // head would have every pass wait there, behind its own requests)
+        GQ_PIN_UNIFORM64(xi);
+        GQ_PIN_UNIFORM64(xj);
+    }
+    // (the rows through a pointer that walks the table: two scalar adds per
+    // pair in place of an index's shifts and adds.  Opaque at the top of each
+    // pair, so a pair's eight reads -- 64 bytes on end from its T_W -- are one
+    // request and are not merged with another pair's.)
+    TP row = tab + tab_at(0, ka);
+    auto pair = [&](int k) {
+        R w = 0, wa = 0, wxi = 0, wxj = 0, wm = 0, wx = 0, nxi = 0, nxj = 0;
+        if constexpr (ROWS) {
+            GQ_PIN_UNIFORM64(row);
+            w = row[tab_at(T_W, 0)]; wa = row[tab_at(T_WA, 0)];
+            wxi = row[tab_at(T_WXI, 0)]; wxj = row[tab_at(T_WXJ, 0)];
+            wm = row[tab_at(T_WM, 0)]; wx = row[tab_at(T_WX, 0)];
+            nxi = row[tab_at(T_XI, 1)];
+            nxj = row[tab_at(T_XJ, 1)];
+            row += tab_at(0, 1);
+            GQ_SCHED_FENCE;
+        } else {
+            xi = tab[tab_at(T_XI, k)];
+            xj = tab[tab_at(T_XJ, k)];
+        }
+        const R p = fma(c.A, xi, c.B * xj);
+        const R dp = c.C + p, dm = c.C - p;
+        const R qp = fma(dp, dp, eps), qm = fma(dm, dm, eps);
+        R fp, fm;
+        if constexpr (ROOTS) {
+            RootStaged<R> rp, rm;
+            rp.begin(qp);
+            rm.begin(qm);
+            rp.template stage<1>(); rm.template stage<1>();
+            rp.template stage<2>(); rm.template stage<2>();
+            rp.template stage<3>(); rm.template stage<3>();
+            rp.template stage<4>(); rm.template stage<4>();
+            fp = rp.end();
+            fm = rm.end();
+        } else {
+            fp = GQ_SQRT(qp);
+            fm = GQ_SQRT(qm);
+        }
+        if constexpr (ROWS) {
+            const R fs = fp + fm, fd = fp - fm;  // add_pair on the weights read above
+            S.s0 = fma(w, fs, S.s0);
+            S.sxi = fma(wxi, fd, S.sxi);
+            S.sxj = fma(wxj, fd, S.sxj);
+            S.sa = fma(wa, fs, S.sa);
+            S.sm = fma(wm, fs, S.sm);
+            S.sx = fma(wx, fs, S.sx);
+            xi = nxi;
+            xj = nxj;
+            GQ_SCHED_FENCE;
+        } else {
+            S.add_pair(tab, k, fp, fm);
+        }
+    };
+    int k = ka;
+    GQ_PAIR_UNROLL_K(1)
+    for (; k + 1 < kb; k += 2) {
+        pair(k);
+        pair(k + 1);
+    }
+    if (k < kb) pair(k);
+    if (centre && (K2 & 1)) {
+        const int kc = K2 >> 1;
+        if constexpr (!ROWS) {
+            xi = tab[tab_at(T_XI, kc)];
+            xj = tab[tab_at(T_XJ, kc)];
+        }
+        const R d = fma(c.A, xi, fma(c.B, xj, c.C));
+        S.add(tab, kc, GQ_SQRT(fma(d, d, eps)));
+    }
+}
 template <bool CLAMP, int UNR, typename TP, typename TV, typename IP>
 GQ_HD Sums<double> node_sums_lut(TP tab, int k0, int K2, int dk, const TV &V, IP I1, int Mo, int No, double eps,
                                  const NodeCoef<double> &c, double u1, double u2, int m, int n)

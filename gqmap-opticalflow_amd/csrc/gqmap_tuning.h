@@ -98,6 +98,19 @@
 #ifndef GQ_FIXSUM_DPP
 #define GQ_FIXSUM_DPP 1
 #endif
+// GQ_EDGE_SCHED: the same item's edge pair loop scheduled by hand
+// (gqmap_math.h edge_sums_range_sched; iter_tile TRIM_EDGE_SCHED; own jobs,
+// halo slices and grouped items alike), a sum of
+//   1  the table rows: XI / XJ a pair ahead, the six weights requested at the
+//      top of the pair and awaited at its sums, through a row pointer that
+//      walks the table -- C2 fp64 -1.4 / -1.6 / -1.6% in three sessions,
+//      every round ahead
+//   2  a pair's two square roots stage by stage side by side -- alone +0.0 to
+//      +0.9%, on top of 1 +0.0 / +0.3%: off
+// 0 keeps edge_sums_range.  profiles/edge_sched_ab.txt, DESIGN.md 4, 8.
+#ifndef GQ_EDGE_SCHED
+#define GQ_EDGE_SCHED 1
+#endif
 // Persistent grid barrier and the dataflow launch's waits: s_sleep between polls
 #ifndef GQ_PERSIST_SLEEP
 #define GQ_PERSIST_SLEEP 2
